@@ -10,6 +10,11 @@ N x 1024 samples, configs[3] at N=8).  Metric: exons*samples/s (BASELINE.json.me
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 launched with
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per GPU,
 RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run times the headline only: set-up, warm-up, the K timed steps, the line.  `--full` adds the
+legs after the timed region (kernel-alone launches, the check against the CPU checker, other modes,
+sizes and configurations, host-fed steps, the workflow, the CPU baseline).  `--dump-outputs DIR`
+writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -258,6 +263,52 @@ def verify_against_oracle(ed, eddist, torch, dev, co, batches, last_ticket, n_ba
                    % (len(cols), len(slabs), "likelihood values vs the checker's LIBM flavour (the reference's arithmetic), 1e-10 RELATIVE with no absolute floor (loglik_needed_abs_floor: values among those beyond it that a 1e-12 floor would have let through)"
                       if tables else "likelihood bits vs the checker's portable flavour"))
     return out
+
+
+DUMP_COLUMN_BYTES = 44 << 20     # --dump-outputs: likelihood matrix + Viterbi states of the sampled columns (8 at 200 000 exons)
+DUMP_CALL_BYTES = 16 << 20       # ... the call table and its statistics; the per-sample parameters take the rest of 64 MiB
+
+
+def dump_outputs(out_dir, torch, eddist, dev, co, ticket, E, S, seed=20250620):
+    """What a caller of the timed path receives for the last timed slab, as float64 / float32 .npy files under out_dir: the
+    per-sample parameters the slab used (phi, expected; phi_bins and edges with the depth-binned model), the call table and its
+    statistics one file per field (calls_<field>.npy, rows sorted by sample and first exon), and for a fixed, seeded choice of
+    sample columns (sample_columns.npy) the likelihood matrix (loglik.npy, exons x 3 x columns) and the Viterbi states (path.npy,
+    exons x columns).  Inputs are seeded, so two builds given the same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    res = co.results(ticket, S, info=True)
+    out = {k: res[k].astype(np.float64) for k in ("phi", "expected", "phi_bins", "edges") if k in res}
+    calls, info = res["calls"], res["info"]
+    rows = np.lexsort((calls["start_exon"], calls["sample"]))
+    row_bytes = 8 * (len(calls.dtype.names) + len(info.dtype.names))
+    if len(rows) * row_bytes > DUMP_CALL_BYTES:
+        rows = rows[np.sort(rng.choice(len(rows), DUMP_CALL_BYTES // row_bytes, replace=False))]
+    for table in (calls, info):
+        for f in table.dtype.names:
+            out["calls_" + f] = table[f][rows].astype(np.float64)
+    col_bytes = E * (3 * 8 + 4)
+    cols = np.sort(rng.choice(S, min(S, 8, max(1, DUMP_COLUMN_BYTES // col_bytes)), replace=False))
+    exons = None
+    if col_bytes * len(cols) > DUMP_COLUMN_BYTES:
+        exons = np.sort(rng.choice(E, DUMP_COLUMN_BYTES // (len(cols) * (3 * 8 + 4) + 8), replace=False))     # (+ 8: exon_rows itself)
+        out["exon_rows"] = exons.astype(np.float64)
+    b, _, _ = co.batch(ticket)
+    ptr = b.device_pointers()
+    if not ptr["loglik"] or not ptr["path"]:
+        raise RuntimeError("--dump-outputs: the last slab's likelihood matrix or Viterbi path is not available")
+    torch.cuda.synchronize()      # (in the sample-major mode the [E][3][S] form is made on the batch's own stream when its pointer is asked for)
+    ct = torch.as_tensor(cols, device=dev)
+    ll = _device_view(torch, eddist, ptr["loglik"], (E, 3, S), "<f8", dev)[:, :, ct]
+    path = _device_view(torch, eddist, ptr["path"], (E, S), "|u1", dev)[:, ct]
+    if exons is not None:
+        et = torch.as_tensor(exons, device=dev)
+        ll, path = ll[et], path[et]
+    out["sample_columns"] = cols.astype(np.float64)
+    out["loglik"] = ll.cpu().numpy()
+    out["path"] = path.cpu().numpy().astype(np.float32)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 EMIT_MODES = {"strict": 0, "tables-tile": 1, "tables": 2}
@@ -789,7 +840,7 @@ def main():
     ap.add_argument("--counts-layout", type=int, default=-1, help="1: the device count matrices are handed over sample-major, [samples][exons] -- "
                     "the memory image of R's column-major exons x samples matrix (emit mode tables only: no transposition inside the step); "
                     "0: [exons][samples]; -1 (default): 1 with --emit-mode tables, else 0")
-    ap.add_argument("--strict-steps", type=int, default=6, help="with --emit-mode tables: timed steps of the same workload in strict mode and in "
+    ap.add_argument("--strict-steps", type=int, default=6, help="--full with --emit-mode tables: timed steps of the same workload in strict mode and in "
                     "tables mode with [exons][samples] inputs, run after the timed region and reported under extra (0 = skip)")
     ap.add_argument("--fused", type=int, default=0, help="1: emissions + Viterbi as one kernel (csrc/edfused.inc)")
     ap.add_argument("--keep-loglik", type=int, default=1, help="fused mode: 0 = do not materialise the likelihood matrix")
@@ -807,7 +858,7 @@ def main():
                     "the emissions of the following groups (the lone-batch schedule); -1 = the library's default")
     ap.add_argument("--fit-priority", type=int, default=0, help="priority of the stream the fit runs on in pipelined mode (0 = normal; -1 = high: "
                     "the fit then pushes into the running emission launch and costs it more than it saves, 12.2 against 11.5 ms)")
-    ap.add_argument("--kernel-alone", type=int, default=1, help="1 (default): after the timed region, time three emission launches with the GPU to "
+    ap.add_argument("--kernel-alone", type=int, default=1, help="1 (default): with --full, after the timed region, time three emission launches with the GPU to "
                     "themselves (roofline.kernel_ms_alone); 0: skip (profiling passes, so that per-kernel averages contain the live launches only)")
     ap.add_argument("--pretouch-streams", type=int, default=0, help="(diagnostic) use that many unrelated streams before the pipeline's streams are first used")
     ap.add_argument("--hw-queues", type=int, default=0, help="(diagnostic) GPU_MAX_HW_QUEUES for this process unless the environment already sets it "
@@ -824,28 +875,33 @@ def main():
                     "0 = ordinary streams (-1 = the library's default, 1)")
     ap.add_argument("--tables-early", type=int, default=-1, help="cohort driver: 1 = a slab's per-sample constants and tables are made right behind its "
                     "fit on the fit stream, 0 = at the boundary between two emission launches (-1 = the library's default, 0)")
-    ap.add_argument("--stage-inputs", type=int, default=1, help="1 (default, N = 1 only): additionally time the same steps with the counts uploaded from "
+    ap.add_argument("--stage-inputs", type=int, default=1, help="1 (default, N = 1 only): with --full, additionally time the same steps with the counts uploaded from "
                     "host memory for every slab (copy stream, double-buffered device slabs): reported as value_with_h2d, never as value; 0: skip")
     ap.add_argument("--wire", type=int, default=2, help="--stage-inputs: bytes per count on the link (2 = uint16 widened on the device, 4 = int32)")
-    ap.add_argument("--fit-concordance", type=int, default=64, help="columns of the batch on which the whole path is run twice after the timed "
+    ap.add_argument("--fit-concordance", type=int, default=64, help="--full: columns of the batch on which the whole path is run twice after the timed "
                     "region -- maximum-likelihood fit vs aod::betabin's Nelder-Mead procedure -- and the differences counted (0 = skip)")
-    ap.add_argument("--config1-steps", type=int, default=20, help="timed steps of the BASELINE configs[1] leg (200 000 x 64, phi given) run after "
+    ap.add_argument("--config1-steps", type=int, default=20, help="--full: timed steps of the BASELINE configs[1] leg (200 000 x 64, phi given) run after "
                     "the headline and reported under extra.config1 (0 = skip)")
-    ap.add_argument("--verify-columns", type=int, default=4, help="columns of the last slabs checked against the CPU oracle after the timed region (0 = skip)")
+    ap.add_argument("--verify-columns", type=int, default=4, help="--full: columns of the last slabs checked against the CPU oracle after the timed region (0 = skip)")
     ap.add_argument("--batches-in-flight", type=int, default=6, help="slabs in flight in the library's cohort pipeline = batch objects used in rotation (>= 2).  "
                     "6 (default): three LANES of two slots -- independent pipelines inside the cohort object, one lane's emission launch fills the CUs that "
                     "another's table build and chains leave idle (profiles/r05_ab_lanes.txt, one box: 3.72-3.81 ms per step; 4 = two lanes: 3.79-3.90; "
                     "2 = one lane, round 4's form: 4.17-4.20; 8: 4.2)")
-    ap.add_argument("--workflow-reps", type=int, default=3, help="after the timed region (N = 1): the reference's workflow for one cohort end to end -- "
+    ap.add_argument("--workflow-reps", type=int, default=3, help="--full, after the timed region: the reference's workflow for one cohort end to end -- "
                     "upload, reference sets, calls -- reported under extra.workflow; 0: skip")
-    ap.add_argument("--regimes", type=int, default=1, help="1 (default, N = 1, the default workload only): the headline's step at depths 25 / 400 / 1600 and at 64 / 256 samples "
+    ap.add_argument("--regimes", type=int, default=1, help="1 (default, --full, N = 1, the default workload only): the headline's step at depths 25 / 400 / 1600 and at 64 / 256 samples "
                     "per slab, each with table statistics and the check against the CPU checker: extra.regimes")
-    ap.add_argument("--dropin", type=int, default=1, help="1 (default, N = 1): time the two reference-shaped entries (ed_get_loglike_matrix on all exons of a sample, ed_hmm on the "
+    ap.add_argument("--dropin", type=int, default=1, help="1 (default, --full, N = 1): time the two reference-shaped entries (ed_get_loglike_matrix on all exons of a sample, ed_hmm on the "
                     "longest / a median chromosome, the 1 + 24-call sequence of one sample) next to the CPU port: extra.dropin")
     ap.add_argument("--lib-variant", default="", help="load exomedepth_amd/libedcore_<name>.so instead of libedcore.so (experiments only)")
     ap.add_argument("--cpu-all-cores", type=int, default=1, help="1: also time the CPU baseline with one sample per host core "
                     "(process-level parallelism; reported inside cpu_baseline.all_cores)")
-    ap.add_argument("--cpu-samples", type=int, default=12, help="columns timed on the host for cpu_baseline (0 = skip)")
+    ap.add_argument("--cpu-samples", type=int, default=12, help="--full: columns timed on the host for cpu_baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the legs that check and extend the headline (each "
+                    "under its own option above): kernel alone, verify, fit concordance, configs[1], host-fed steps, workflow, drop-in entries, regimes, "
+                    "other modes, CPU baseline.  Without it a run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed as .npy files "
+                    "under DIR (cohort driver; rank 0's slab): per-sample parameters, call table, likelihoods and Viterbi states of sampled columns")
     args = ap.parse_args()
     if args.cov > 0 or args.phi_bins > 1 or args.fused:      # the table-driven mode serves the default model (per-sample phi and expected)
         args.emit_mode = "strict"
@@ -862,6 +918,8 @@ def main():
         os.environ.setdefault("GPU_MAX_HW_QUEUES", str(args.hw_queues))
 
     if args.driver == "multi-device":
+        if args.dump_outputs:
+            ap.error("--dump-outputs needs the cohort driver")
         return multi_device_main(args)
 
     import torch
@@ -948,6 +1006,8 @@ def main():
     plain = args.cov == 0 and args.phi_bins == 1
     bins_cohort = args.driver == "cohort" and args.cov == 0 and args.phi_bins > 1 and args.fit and not args.fused
     use_cohort = args.driver == "cohort" and (plain or bins_cohort) and not args.fused
+    if args.dump_outputs and not use_cohort:
+        ap.error("--dump-outputs needs the cohort driver")
     step_no = [0]
     if use_cohort:
         # The library's cohort pipeline: every step is ONE submission (ed_cohort_submit); the library owns the streams, rotates
@@ -1112,6 +1172,8 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:       # before anything else is submitted: the last timed slab's results are still in its batch object
+        dump_outputs(args.dump_outputs, torch, eddist, dev, co, last_ticket[0], E, S)
 
     cells_per_step = E * S * world
     value = cells_per_step * args.steps / elapsed
@@ -1136,7 +1198,7 @@ def main():
     # (outside the timed region) the emission launches with the GPU to themselves: one slab, given phi, nothing queued on
     # other streams -- what the kernel takes when it does not host the next slab's fit and the previous slab's chains
     alone_ms = None
-    if plain and not args.fused and args.pipeline and rank == 0 and args.kernel_alone:
+    if args.full and plain and not args.fused and args.pipeline and rank == 0 and args.kernel_alone:
         if use_cohort:
             b_last, pp, pe = co.batch(last_ticket[0])
             par = (ed.api._RawDevice(pp), ed.api._RawDevice(pe)) if args.fit else (phi, p)
@@ -1154,7 +1216,7 @@ def main():
                 bb.wait()
             alone_ms = bb.stage_ms()["emissions"]
 
-    # ---- after the timed region: the bench checks what it timed, and carries the legs the headline does not -----------------
+    # ---- after the timed region (--full): the bench checks what it timed, and carries the legs the headline does not --------
     # A leg that fails on ONE rank must not cost the line its headline (measured above): it reports {"error": ...} instead.  (With several
     # ranks a leg holds collectives -- a rank that skipped the rest of it would leave the others waiting -- so there a failure stays fatal.)
     def leg(fn, *a, **k):
@@ -1166,7 +1228,7 @@ def main():
             import traceback
             return {"error": "%s: %s" % (type(e).__name__, e), "where": traceback.format_exc().strip().splitlines()[-3:]}
     verify = None
-    if world == 1 and args.verify_columns > 0 and plain and not args.fused:      # (N = 1 only, like cpu_baseline: the other ranks would wait)
+    if args.full and world == 1 and args.verify_columns > 0 and plain and not args.fused:      # (N = 1 only, like cpu_baseline: the other ranks would wait)
         verify = leg(verify_against_oracle, ed, eddist, torch, dev, co if use_cohort else None, batches, last_ticket[0] if use_cohort else None,
                                        n_batches, test, ref, phi, p, phi_fit if not use_cohort else None, p_fit if not use_cohort else None,
                                        bool(args.fit), chrom_off, start, end, args.verify_columns, tables=args.emit_mode != "strict")
@@ -1177,32 +1239,32 @@ def main():
         co.close()
         co = None
     fit_conc = None
-    if world == 1 and args.fit and plain and not args.fused and args.fit_concordance > 0:
+    if args.full and world == 1 and args.fit and plain and not args.fused and args.fit_concordance > 0:
         from exomedepth_amd import concordance
         k = min(args.fit_concordance, S)
         fit_conc = leg(concordance.fit_mode_concordance, plan, test[:, :k].contiguous(), ref[:, :k].contiguous())
     config1 = None
-    if world == 1 and args.config1_steps > 0 and plain and not args.fused and S >= 64:
+    if args.full and world == 1 and args.config1_steps > 0 and plain and not args.fused and S >= 64:
         config1 = leg(config1_leg, ed, torch, plan, test, ref, phi, p, E, args.config1_steps, mode_opts(args))
     staged = None
-    if world == 1 and args.stage_inputs and use_cohort:
+    if args.full and world == 1 and args.stage_inputs and use_cohort:
         staged = leg(staged_leg, ed, torch, plan, test, ref, phi, p, E, S, min(n_batches, 2), args)     # (host-fed slabs: two / three slabs in flight, one lane -- the link is the bound)
     if staged is not None and "error" not in staged and args.emit_mode == "tables" and args.counts_layout == 1:
         staged["r_entry"] = leg(r_entry_leg, ed, chrom_off, start, end, test, ref, S, max(2, args.steps // 3), args.fit, phi, p)
     workflow = None
-    if args.workflow_reps > 0 and plain and args.fit and not args.fused and S >= 64 and (world == 1 or use_pg):
+    if args.full and args.workflow_reps > 0 and plain and args.fit and not args.fused and S >= 64 and (world == 1 or use_pg):
         workflow = leg(workflow_leg, ed, torch, plan, test, start, end, E, S, args.workflow_reps, EMIT_MODES[args.emit_mode], world, rank, eddist)
     dropin = None
-    if world == 1 and args.dropin and plain and not args.fused:
+    if args.full and world == 1 and args.dropin and plain and not args.fused:
         dropin = leg(dropin_leg, ed, chrom_off, start, end, test[:, :2].cpu().numpy(), ref[:, :2].cpu().numpy(), phi.cpu().numpy(), p.cpu().numpy())
     regimes = None
-    if world == 1 and args.regimes and use_cohort and plain and not args.fused and args.emit_mode == "tables" and (E, S, int(args.depth)) == (200_000, 1024, 100):
+    if args.full and world == 1 and args.regimes and use_cohort and plain and not args.fused and args.emit_mode == "tables" and (E, S, int(args.depth)) == (200_000, 1024, 100):
         regimes = []
         for (dpt, ss) in ((25.0, 1024), (400.0, 1024), (1600.0, 1024), (100.0, 256), (100.0, 64)):
             regimes.append(leg(regime_leg, ed, eddist, torch, dev, plan, chrom_off, start, end, E, ss, dpt, args.fit, {k: v for k, v in opts_headline.items() if k != "timing"},
                                n_batches, 8, 20250620 + 3 + int(dpt) + ss, 2))
     other_modes = None
-    if world == 1 and args.strict_steps > 0 and plain and not args.fused and use_cohort and args.emit_mode == "tables":
+    if args.full and world == 1 and args.strict_steps > 0 and plain and not args.fused and use_cohort and args.emit_mode == "tables":
         other_modes = {"strict": leg(mode_leg, ed, torch, plan, test, ref, S, args.strict_steps, args.fit, phi, p, {}),
                        "fit_mode_1": (leg(mode_leg, ed, torch, plan, test, ref, S, args.strict_steps, True, phi, p, {**mode_opts(args), "fit_mode": 1})
                                       if args.fit and args.fit_mode == 0 else None),
@@ -1303,7 +1365,7 @@ def main():
             if "value_with_h2d" in staged:
                 out["value_with_h2d"] = staged.pop("value_with_h2d")
             out["h2d"] = staged
-        if world == 1 and args.cpu_samples > 0:
+        if args.full and world == 1 and args.cpu_samples > 0:
             k = min(args.cpu_samples, S)
             ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             out["cpu_baseline"] = leg(cpu_baseline, test[:, :k].cpu().numpy(), ref[:, :k].cpu().numpy(),

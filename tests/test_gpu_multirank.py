@@ -20,7 +20,7 @@ def test_two_ranks_share_one_gpu_and_gather_their_call_tables(edlib):
     E, S, C = 20000, 128, 24
     env = dict(os.environ, ED_BENCH_SHARE_GPU="1", ED_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29641", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--master-port", "29641", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--exons", str(E), "--samples", str(S), "--cpu-samples", "0", "--verify-columns", "0", "--fit-concordance", "0",
            "--config1-steps", "0", "--kernel-alone", "0", "--stage-inputs", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
@@ -65,7 +65,7 @@ def test_one_rank_over_rccl(edlib):
     """A process group of ONE rank over RCCL on the box's GPU (ED_BENCH_FORCE_PG=1): the collectives of the N > 1 path as RCCL runs them -- barrier, the
     MAX all-reduce of the clock, the gather of the call tables from DEVICE memory, and the workflow leg's all_gather_into_tensor of the count slabs -- the
     branches the two-ranks-on-one-GPU test (gloo, host memory) cannot reach.  Same calls, same reference choices as the run without a group."""
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--exons", "20000", "--samples", "128",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--exons", "20000", "--samples", "128",
             "--cpu-samples", "0", "--verify-columns", "0", "--fit-concordance", "0", "--config1-steps", "0", "--kernel-alone", "0", "--stage-inputs", "0",
             "--strict-steps", "0", "--workflow-reps", "1"]
     out = {}
