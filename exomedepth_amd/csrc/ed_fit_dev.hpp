@@ -138,7 +138,7 @@ __device__ __forceinline__ void digamma_trigamma_nolog_big(double x, double& psi
 // accumulate_cell for a run of cells (k_fit_accum).  The gradient needs sum_e ln(x1 / x3) and sum_e ln(x2 / x3): the ratios of a run are MULTIPLIED
 // (pa, pb) and the caller takes one logarithm per run of eight cells instead of two per cell -- ln of a product of eight factors carries the same
 // ~1e-15 of absolute error as the sum of eight rounded logarithms, and the factors (>= 10 / 2^31 each: the arguments come back shifted to >= 10)
-// cannot leave the range.  `big`: wave-uniform, every lane's three arguments are >= 32 (the short series).
+// cannot leave the range.  `big`: this lane's three arguments are >= 32 (the short series); lanes of one wave may differ.
 // (Round 6 also built the test-count terms from per-test histograms shared by the K prefixes of the cohort reference sets -- one reciprocal per distinct
 // count instead of a digamma + trigamma evaluation per cell, review r5 item 2 -- and measured nothing: 13.95 against 13.95 ms for the stage, same box,
 // alternating.  After the two changes above the stage is no longer bound by this kernel (4.6 of its 14 ms); the form is not in the tree.)

@@ -1440,13 +1440,15 @@ k_fit_accum(const int32_t* __restrict__ test, int64_t trs, int64_t tcs, const in
       rb[k] = (en < e1) ? ref[en * rrs + s] : 0;
     }
     // one logarithm per run of kPre cells and gradient component (ed_fit_dev.hpp: accumulate_cell_run); the short digamma / trigamma series when
-    // every lane's arguments of the run are large (the lanes of a wave are 64 columns at the SAME exons: deep or shallow together)
+    // THIS lane's arguments of the run are all large.  The choice is the lane's own: a wave-wide vote made a column's sums depend on which columns
+    // shared its wave (k_fit_compact packs them in atomic order), and the two series differ in the last bits (tests/test_gpu_fit_invariance.py).
+    // A wave with lanes of both kinds runs both branches.
     double small = 1e300;
 #pragma unroll
     for (int k = 0; k < kPre; ++k) {
       if (e + (int64_t)k * stride < e1 && yc[k] + rc[k] > 0) small = fmin(small, fmin(a + (double)yc[k], b + (double)rc[k]));
     }
-    const bool big = __all(small >= 32.0) != 0;           // (th + n >= a + y)
+    const bool big = small >= 32.0;                       // (th + n >= a + y)
     double pa = 1.0, pb = 1.0;
 #pragma unroll
     for (int k = 0; k < kPre; ++k) {
@@ -3037,7 +3039,8 @@ static int fit_columns(FitWork& w, const int32_t* d_test, int64_t trs, int64_t t
   const int coarse = (E >= 8192) ? kFitCoarsePasses : 0;   // a stride-16 subset below ~500 exons is too noisy to help
   const int cstride = 16;                   // (8 / 4 / 2 measured on the cohort reference sets' 10 000-row fit: 9.9 / 11.1 / 12.3 ms against 9.6)
   // Prefixes closed before the first pass (k_fit_skip_prefixes) are lanes that idle through every pass: the columns that iterate are packed from the
-  // start then (round 6), and again before each of the first full passes as columns converge.  Which slot a column takes does not show in its sums.
+  // start then (round 6), and again before each of the first full passes as columns converge.  Which slot a column takes does not show in its sums:
+  // k_fit_accum picks its digamma series per lane, and k_fit_update reduces a slot's partials in chunk order (tests/test_gpu_fit_invariance.py).
   const bool can_pack = S >= 4096 && w.colmap;
   const bool pack_early = can_pack && skip_K > 0 && tmod > 0 && d_skip_from && ED_FIT_PACK_EARLY;
   auto compact = [&]() {

@@ -22,6 +22,20 @@ def _cohort(E=20000, S=64, seed=7, depth=90.0):
 
 @pytest.mark.parametrize("nred", [0, 5000])
 def test_cohort_selection_equals_one_call_per_sample(edlib, nred):
+    _cohort_against_single_calls(edlib, nred, bitwise=False)
+
+
+@pytest.mark.parametrize("nred", [0, 5000])
+def test_row_major_cohort_selection_equals_one_call_per_sample_bit_for_bit(edlib, monkeypatch, nred):
+    """The cohort's row-major form and the single-test entry fit the cumulative references with the same per-cell arithmetic (fit_columns: the
+    same rows, the same moment start, the same step tolerance kFitStepTol; k_fit_accum's digamma series chosen per column, not per wave): phi and
+    mean_p of every prefix the R loop reaches are the same bits, the other statistics held as in the column-major comparison."""
+    monkeypatch.setenv("ED_REFCOHORT_ROWMAJOR", "1")
+    _cohort_against_single_calls(edlib, nred, bitwise=True)
+    assert edlib.refcohort_last_path()["chunks_row_major"] > 0
+
+
+def _cohort_against_single_calls(edlib, nred, bitwise):
     counts, bl = _cohort()
     E, S = counts.shape
     res = edlib.cohort_select_reference_sets(counts, bl, nred, max_refs=32, want_correlations=True)
@@ -46,6 +60,9 @@ def test_cohort_selection_equals_one_call_per_sample(edlib, nred):
             assert np.array_equal(np.isnan(a), np.isnan(b)), (t, f)
             m = ~np.isnan(a)
             assert np.allclose(a[m], b[m], rtol=tol, atol=0), (t, f, np.max(np.abs(a[m] - b[m]) / np.abs(b[m])))
+            if bitwise and f in ("phi", "mean_p"):
+                ua, ub = a[m].view(np.int64), b[m].view(np.int64)
+                assert np.array_equal(ua, ub), (t, f, "max %d ulp apart" % int(np.max(np.abs(ua - ub))))
         assert np.array_equal(rows["selected"][:k], st["selected"][:k])
         assert np.array_equal(agg[:, t], counts[:, want_choice].sum(axis=1))               # the aggregate reference, every exon
         n_same += 1
