@@ -71,6 +71,7 @@ SYMBOLS = [
     ("ed_batch_run_cov", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_double, _vp]),
     ("ed_batch_expected_cov", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("ed_batch_run", C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _vp]),
+    ("ed_batch_set_mixture", C.c_int, [_vp, _vp]),
     ("ed_batch_set_fused", C.c_int, [_vp, C.c_int]),
     ("ed_batch_keep_loglik", C.c_int, [_vp, C.c_int]),
     ("ed_batch_n_emit_launches", C.c_int, [_vp]),
@@ -106,6 +107,7 @@ SYMBOLS = [
     ("ed_cohort_destroy", None, [_vp]),
     ("ed_cohort_set_option", C.c_int, [_vp, C.c_char_p, _dbl]),
     ("ed_cohort_submit", C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _dbl, _vp, C.POINTER(_i64)]),
+    ("ed_cohort_submit_mix", C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     ("ed_cohort_batch", C.c_int, [_vp, _i64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     ("ed_cohort_copy_params", C.c_int, [_vp, _i64, _vp, _vp]),
     ("ed_cohort_copy_bins_params", C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
@@ -123,6 +125,7 @@ SYMBOLS = [
     ("ed_host_alloc", C.c_int, [C.POINTER(_vp), C.c_size_t]),
     ("ed_host_free", C.c_int, [_vp]),
     ("ed_cohort_run_host", C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _dbl, _vp, _vp, _vp, C.POINTER(_i64)]),
+    ("ed_cohort_run_host_mix", C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     ("ed_cohort_copy_calls", C.c_int, [_vp, _vp, _vp, _i64]),
     ("ed_cohort_run_status", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     ("ed_multi_create", C.c_int, [C.POINTER(_vp), _vp, C.c_int, _i64, _i32, _vp, _vp, _vp, _dbl, _dbl, _i64, C.c_int]),
@@ -130,6 +133,7 @@ SYMBOLS = [
     ("ed_multi_n_devices", C.c_int, [_vp]),
     ("ed_multi_set_option", C.c_int, [_vp, C.c_char_p, _dbl]),
     ("ed_multi_run_host", C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _dbl, _vp, _vp, _vp, C.POINTER(_i64)]),
+    ("ed_multi_run_host_mix", C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     ("ed_multi_copy_calls", C.c_int, [_vp, _vp, _vp, _i64]),
     ("ed_multi_run_status", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     ("ed_multi_table_status", C.c_int, [_vp, C.POINTER(_i64)]),

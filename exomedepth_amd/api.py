@@ -175,6 +175,25 @@ def _device_pointer(x, dtype, keep):
     return d.ptr
 
 
+def _is_device(x):
+    return isinstance(x, (DeviceArray, _RawDevice)) or (hasattr(x, "data_ptr") and getattr(x, "is_cuda", False))
+
+
+def _per_sample_mixture(mixture, n, device_ok=False):
+    """None for a scalar mixture (today's path); otherwise the per-sample form: a float64[n] host array, checked here (one finite value
+    per sample) before any device work -- or, with device_ok, a device array passed through as it is"""
+    if device_ok and _is_device(mixture):
+        return mixture
+    if np.ndim(mixture) == 0:
+        return None
+    m = np.ascontiguousarray(mixture, dtype=np.float64)
+    if m.ndim != 1 or m.size != n:
+        raise ValueError("mixture / prop_tumor must be a scalar or one value per sample (%d), got shape %s" % (n, m.shape))
+    if not np.all(np.isfinite(m)):
+        raise ValueError("mixture / prop_tumor must be finite")
+    return m
+
+
 class Plan:
     """Exon design + HMM parameters (CallCNVs arguments, reference R/class_definition.R:261, :311).
     Exons must be ordered by (chromosome, position); chrom_off delimits the chromosomes."""
@@ -306,6 +325,22 @@ class Batch:
         pe = _device_pointer(expected, np.float64, keep)
         self._keep_run = keep  # keep temporaries alive until the next run
         check(lib().ed_batch_run(self.handle, pt, pr, pp, pe, float(mixture), C.c_void_p(stream or 0)))
+
+    def set_mixture(self, mixture):
+        """One mixture per sample (ed_batch_set_mixture): matched tumour / normal pairs, each at its own tumour fraction.  A host
+        float64[n_samples] (uploaded) or a device array (used in place); the batch keeps it alive.  None turns it off.  While it is set,
+        the `mixture` argument of run*() and verify_emissions*() is ignored."""
+        if mixture is None:
+            check(lib().ed_batch_set_mixture(self.handle, None))
+            self._mix = None
+            return
+        m = _per_sample_mixture(mixture, self.n_samples, device_ok=True)
+        if m is None:
+            raise ValueError("set_mixture takes one value per sample (use the `mixture` argument of run() for one value)")
+        keep = []
+        p = _device_pointer(m, np.float64, keep)
+        check(lib().ed_batch_set_mixture(self.handle, p))
+        self._mix = keep + [mixture]
 
     @property
     def fit_bins_form(self):
@@ -630,19 +665,25 @@ class Cohort:
 
     def submit(self, test, ref, phi=None, expected=None, mixture=1.0, ready_stream=None, n_samples=None):
         """one slab, counts on the device: (n_exons, n) int32 torch CUDA tensors / DeviceArrays (host arrays are uploaded
-        synchronously first -- use submit_host for the staged path).  phi / expected: device float64[n] or None (fit)."""
+        synchronously first -- use submit_host for the staged path).  phi / expected: device float64[n] or None (fit).
+        mixture: a scalar, or one value per sample of the slab (host float64[n], uploaded; or a device array: ed_cohort_submit_mix)."""
         keep = []
         if n_samples is None:
             n_samples = int(test.shape[1])
+        mix = _per_sample_mixture(mixture, int(n_samples), device_ok=True)
         cdt = np.uint16 if getattr(self, "_counts_bits", 32) == 16 else np.int32
         pt = _device_pointer(test, cdt, keep)
         pr = _device_pointer(ref, cdt, keep)
         pp = _device_pointer(phi, np.float64, keep) if phi is not None else None
         pe = _device_pointer(expected, np.float64, keep) if expected is not None else None
         t = C.c_int64(-1)
-        check(lib().ed_cohort_submit(self.handle, pt, pr, int(n_samples), pp, pe, float(mixture), C.c_void_p(ready_stream or 0), C.byref(t)))
+        if mix is None:
+            check(lib().ed_cohort_submit(self.handle, pt, pr, int(n_samples), pp, pe, float(mixture), C.c_void_p(ready_stream or 0), C.byref(t)))
+        else:
+            pm = _device_pointer(mix, np.float64, keep)
+            check(lib().ed_cohort_submit_mix(self.handle, pt, pr, int(n_samples), pp, pe, pm, C.c_void_p(ready_stream or 0), C.byref(t)))
         # the slab's counts are read until its results have been collected (the call decoration): keep them alive that long
-        self._keep[t.value % self.slabs_in_flight] = keep + [test, ref, phi, expected]
+        self._keep[t.value % self.slabs_in_flight] = keep + [test, ref, phi, expected, mixture]
         return t.value
 
     def submit_host(self, test, ref, layout, phi=None, expected=None, mixture=1.0, n_samples=None, row_stride=None):
@@ -756,20 +797,27 @@ class Cohort:
 
     def run_host(self, test, ref, layout, phi=None, expected=None, mixture=1.0, want_path=False):
         """CallCNVs for a whole host-resident cohort (ed_cohort_run_host).  layout 0: (n_exons, S) arrays; layout 1: (S, n_exons)
-        arrays (R's column-major n_exons x S matrix).  Returns dict(calls, info, phi, expected, n_unconverged, n_gsl_errors[, path])."""
+        arrays (R's column-major n_exons x S matrix).  mixture: a scalar, or one value per column (matched tumour / normal pairs:
+        test = tumours, ref = normals; ed_cohort_run_host_mix).  Returns dict(calls, info, phi, expected, n_unconverged,
+        n_gsl_errors[, path])."""
         test, ref = np.ascontiguousarray(test), np.ascontiguousarray(ref)
         if test.dtype != ref.dtype or test.dtype not in (np.dtype(np.int32), np.dtype(np.uint16)):
             raise ValueError("test and ref must both be int32 or both uint16")
         S = int(test.shape[1] if layout == 0 else test.shape[0])
+        mix = _per_sample_mixture(mixture, S)
         E = self.plan.n_exons
         ph = _f64(phi) if phi is not None else None
         ex = _f64(expected) if expected is not None else None
         phi_out, exp_out = np.empty(S), np.empty(S)
         path = np.empty((E, S) if layout == 0 else (S, E), dtype=np.uint8) if want_path else None
         n = C.c_int64(0)
-        check(lib().ed_cohort_run_host(self.handle, C.c_void_p(test.ctypes.data), C.c_void_p(ref.ctypes.data), S, int(layout),
-                                       int(test.dtype.itemsize), _ptr(ph) if ph is not None else None, _ptr(ex) if ex is not None else None,
-                                       float(mixture), _ptr(phi_out), _ptr(exp_out), _ptr(path) if path is not None else None, C.byref(n)))
+        args = (self.handle, C.c_void_p(test.ctypes.data), C.c_void_p(ref.ctypes.data), S, int(layout), int(test.dtype.itemsize),
+                _ptr(ph) if ph is not None else None, _ptr(ex) if ex is not None else None)
+        outs = (_ptr(phi_out), _ptr(exp_out), _ptr(path) if path is not None else None, C.byref(n))
+        if mix is None:
+            check(lib().ed_cohort_run_host(*args, float(mixture), *outs))
+        else:
+            check(lib().ed_cohort_run_host_mix(*args, _ptr(mix), *outs))
         calls = np.zeros(n.value, dtype=CALL_DTYPE)
         info = np.zeros(n.value, dtype=CALL_INFO_DTYPE)
         check(lib().ed_cohort_copy_calls(self.handle, _ptr(calls), _ptr(info), n.value))
@@ -829,20 +877,26 @@ class MultiDevice:
             pass
 
     def run_host(self, test, ref, layout, phi=None, expected=None, mixture=1.0, want_path=False):
-        """as Cohort.run_host; the result also carries `devices`: per device the slabs / columns it took from the queue, its thread's seconds, its NUMA node"""
+        """as Cohort.run_host (mixture: a scalar or one value per column); the result also carries `devices`: per device the slabs /
+        columns it took from the queue, its thread's seconds, its NUMA node"""
         test, ref = np.ascontiguousarray(test), np.ascontiguousarray(ref)
         if test.dtype != ref.dtype or test.dtype not in (np.dtype(np.int32), np.dtype(np.uint16)):
             raise ValueError("test and ref must both be int32 or both uint16")
         S = int(test.shape[1] if layout == 0 else test.shape[0])
+        mix = _per_sample_mixture(mixture, S)
         E = self.n_exons
         ph = _f64(phi) if phi is not None else None
         ex = _f64(expected) if expected is not None else None
         phi_out, exp_out = np.empty(S), np.empty(S)
         path = np.empty((E, S) if layout == 0 else (S, E), dtype=np.uint8) if want_path else None
         n = C.c_int64(0)
-        check(lib().ed_multi_run_host(self.handle, C.c_void_p(test.ctypes.data), C.c_void_p(ref.ctypes.data), S, int(layout),
-                                      int(test.dtype.itemsize), _ptr(ph) if ph is not None else None, _ptr(ex) if ex is not None else None,
-                                      float(mixture), _ptr(phi_out), _ptr(exp_out), _ptr(path) if path is not None else None, C.byref(n)))
+        args = (self.handle, C.c_void_p(test.ctypes.data), C.c_void_p(ref.ctypes.data), S, int(layout), int(test.dtype.itemsize),
+                _ptr(ph) if ph is not None else None, _ptr(ex) if ex is not None else None)
+        outs = (_ptr(phi_out), _ptr(exp_out), _ptr(path) if path is not None else None, C.byref(n))
+        if mix is None:
+            check(lib().ed_multi_run_host(*args, float(mixture), *outs))
+        else:
+            check(lib().ed_multi_run_host_mix(*args, _ptr(mix), *outs))
         calls = np.zeros(n.value, dtype=CALL_DTYPE)
         info = np.zeros(n.value, dtype=CALL_INFO_DTYPE)
         check(lib().ed_multi_copy_calls(self.handle, _ptr(calls), _ptr(info), n.value))
@@ -1044,6 +1098,22 @@ class ExomeDepth:
                           "reads.ratio": _signif(ratio, 3)})
         self.CNV_calls = calls
         return self
+
+
+def somatic_CNV_call(normal, tumor, prop_tumor=1.0, chromosome=None, start=None, end=None, names=None):
+    """reference R/class_definition.R:442-461: one matched tumour / normal pair -- new('ExomeDepth', test = tumor, reference = normal,
+    prop.tumor = prop_tumor) (the fit ignores prop_tumor; the likelihood sees it) followed by CallCNVs(transition.probability = 1e-4)
+    with the default expected.CNV.length.  Returns the ExomeDepth object.  A cohort of pairs, each at its own tumour fraction:
+    Cohort.run_host / MultiDevice.run_host with test = tumours, ref = normals and one mixture per column."""
+    if chromosome is None or start is None or end is None or names is None:
+        raise ValueError("chromosome, start, end and names are required (R/class_definition.R:442)")
+    if np.ndim(prop_tumor) != 0:
+        raise ValueError("prop_tumor is one value for the pair")
+    sys.stderr.write("Warning: this function is largely untested and experimental\n")     # message() lines of :444-451
+    sys.stderr.write("Initializing the exomeDepth object\n")
+    x = ExomeDepth(test=tumor, reference=normal, prop_tumor=prop_tumor, formula="cbind(test, reference) ~ 1")
+    sys.stderr.write("Now calling the CNVs\n")
+    return x.CallCNVs(chromosome, start, end, names, transition_probability=1e-4)
 
 
 REFSET_DTYPE = np.dtype([("ref_index", "<i4"), ("selected", "<i4"), ("correlation", "<f8"), ("expected_BF", "<f8"),

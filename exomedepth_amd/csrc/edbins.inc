@@ -439,7 +439,7 @@ __device__ __forceinline__ void emit_bins_tile(const int32_t* __restrict__ test,
             const double* __restrict__ phib, const double* __restrict__ expected, const double* __restrict__ X, int K,
             const double* __restrict__ beta, double mixture, int64_t E, int64_t S, double* __restrict__ loglik,
             unsigned long long* __restrict__ nerr, const double* __restrict__ ctab, int rtab, const uint8_t* __restrict__ left_out,
-            int64_t bx, int64_t blk, int64_t gx)
+            int64_t bx, int64_t blk, int64_t gx, const double* __restrict__ mix_s)
 {
   // B > 0: phi interpolated from the depth levels (phib = phi.estimates); B == 0: phib = one phi per sample.
   // K >= 0: expected = plogis(X beta) per exon (edcov.inc); K < 0: `expected` holds one value per sample.
@@ -487,7 +487,7 @@ __device__ __forceinline__ void emit_bins_tile(const int32_t* __restrict__ test,
     }
     const double sd = __builtin_sqrt((phi * ex) * (1. - ex));
     double ep[3];
-    state_props(ex, mixture, ep);
+    state_props(ex, (mix_s && s < S) ? mix_s[s] : mixture, ep);   // mix_s: one mixture per sample (ed_batch_set_mixture)
 #pragma unroll
     for (int st = 0; st < 3; ++st) shape_params(ep[st], sd, a1[st], a2[st]);
   }
@@ -554,7 +554,7 @@ k_emit_bins(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, i
             const double* __restrict__ phib, const double* __restrict__ expected, const double* __restrict__ X, int K,
             const double* __restrict__ beta, double mixture, int64_t E, int64_t S, double* __restrict__ loglik,
             unsigned long long* __restrict__ nerr, const double* __restrict__ ctab, int rtab, const uint8_t* __restrict__ left_out,
-            const int* __restrict__ skip, int tiles_per_wg, int64_t n_blk)
+            const int* __restrict__ skip, int tiles_per_wg, int64_t n_blk, const double* __restrict__ mix_s)
 {
   if (skip && *skip) return;
   const int64_t wg = (int64_t)blockIdx.y + (int64_t)blockIdx.z * 65535;
@@ -562,7 +562,7 @@ k_emit_bins(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, i
     const int64_t blk = wg * tiles_per_wg + t;
     if (blk >= n_blk) break;
     emit_bins_tile(test, ref, B, edges, phib, expected, X, K, beta, mixture, E, S, loglik, nerr, ctab, rtab, left_out, (int64_t)blockIdx.x, blk,
-                   (int64_t)gridDim.x);
+                   (int64_t)gridDim.x, mix_s);
     __syncthreads();   // the tile's readers are done with the shared arrays
   }
 }
@@ -574,7 +574,7 @@ k_emit_bins(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, i
 // quadrant: phi >= 1 ...) means "not tabulated" and sends its cells to the per-cell kernel, which also counts their GSL errors.
 __global__ void __launch_bounds__(256)
 k_bins_ctab(int B, const double* __restrict__ edges, const double* __restrict__ phib, const double* __restrict__ expected, double mixture,
-            int64_t S, int rtab, double* __restrict__ ctab, const int* __restrict__ skip)
+            int64_t S, int rtab, double* __restrict__ ctab, const int* __restrict__ skip, const double* __restrict__ mix_s)
 {
   if (skip && *skip) return;
   const int64_t s = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
@@ -584,7 +584,7 @@ k_bins_ctab(int B, const double* __restrict__ edges, const double* __restrict__ 
   const double ex = expected[s];
   const double sd = __builtin_sqrt((phi * ex) * (1. - ex));
   double ep[3];
-  state_props(ex, mixture, ep);
+  state_props(ex, mix_s ? mix_s[s] : mixture, ep);
 #pragma unroll 1
   for (int st = 0; st < 3; ++st) {
     double a1, a2;
@@ -602,7 +602,7 @@ __global__ void __launch_bounds__(kEmitBlock)
 k_emit_bins_tab(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, int B, const double* __restrict__ edges,
                 const double* __restrict__ phib, const double* __restrict__ expected, double mixture, int64_t E, int64_t S,
                 const double* __restrict__ ctab, int rtab, double* __restrict__ loglik, uint8_t* __restrict__ left_out,
-                const int* __restrict__ skip, int64_t blk0, int64_t nblk)
+                const int* __restrict__ skip, int64_t blk0, int64_t nblk, const double* __restrict__ mix_s)
 {
   if (skip && *skip) return;
   // (the launch may be one of several pieces of the exon-block range: [blk0, blk0 + nblk))
@@ -645,7 +645,7 @@ k_emit_bins_tab(const int32_t* __restrict__ test, const int32_t* __restrict__ re
       const double ex = expected[s];
       const double sd = __builtin_sqrt((phi * ex) * (1. - ex));
       double ep[3];
-      state_props(ex, mixture, ep);
+      state_props(ex, mix_s ? mix_s[s] : mixture, ep);
 #pragma unroll
       for (int st = 0; st < 3; ++st) {
         double a1, a2;

@@ -365,6 +365,7 @@ struct ed_cohort {
     const int32_t* last_test = nullptr;
     const int32_t* last_ref = nullptr;
     double last_mix = 1.0;
+    const double* last_mix_s = nullptr;   // ... and its per-sample mixtures (ed_cohort_submit_mix), if any
     int lane = 0;
   };
   std::vector<Slot> slots;
@@ -411,6 +412,8 @@ struct ed_cohort {
   ed_stager* stager = nullptr;
   double* d_par = nullptr;           // ed_cohort_run_host with given parameters: (phi[S_total], expected[S_total]) on the device
   int64_t par_cap = 0;
+  double* d_mixv = nullptr;          // ed_cohort_run_host_mix: the per-sample mixtures [S_total] on the device
+  int64_t mixv_cap = 0;
   // results of ed_cohort_run_host
   std::vector<ed_call> calls;
   std::vector<ed_call_info> info;
@@ -433,6 +436,7 @@ static void cohort_free(ed_cohort* c)
   if (c->stager) stager_free(c->stager);
   if (c->epoch) (void)hipEventDestroy(c->epoch);
   if (c->d_par) (void)hipFree(c->d_par);
+  if (c->d_mixv) (void)hipFree(c->d_mixv);
   for (int l = 0; l < ed_cohort::kMaxLanes; ++l) {
     if (c->mains[l]) (void)hipStreamDestroy(c->mains[l]);
     if (c->fits[l]) (void)hipStreamDestroy(c->fits[l]);
@@ -622,6 +626,7 @@ static int cohort_bins_settle(ed_cohort* c, ed_cohort::Slot& sl)
   if (status == 0) { b->bins_unconverged = 0; return ED_OK; }
   if (int rc = batch_ready(b)) return rc;
   hipStream_t main_st = c->mains[sl.lane];
+  b->d_mix = sl.last_mix_s;
   if (int rc = ed_batch_fit_bins(b, sl.last_test, sl.last_ref, c->phi_bins, sl.d_phib, sl.d_edges, sl.d_exp, main_st)) return rc;
   if (int rc = ed_batch_run_bins(b, sl.last_test, sl.last_ref, c->phi_bins, sl.d_phib, sl.d_edges, sl.d_exp, sl.last_mix, main_st)) return rc;
   HIP_TRY(hipEventRecord(sl.emitted, main_st));
@@ -629,9 +634,10 @@ static int cohort_bins_settle(ed_cohort* c, ed_cohort::Slot& sl)
 }
 
 // slab_bits: 0 = the cohort's option counts_bits; 16 / 32 = THIS slab's device counts are uint16 / int32 whatever the option says (host-fed slabs: the
-// library itself chose the format of the slot's buffers)
+// library itself chose the format of the slot's buffers).  d_mix: DEVICE double [n], one mixture per sample of the slab (NULL: `mixture` for all)
 static int cohort_submit(ed_cohort* c, const int32_t* d_test, const int32_t* d_ref, int64_t n, const double* d_phi,
-                         const double* d_expected, double mixture, hipStream_t ready_stream, int64_t* ticket, int slab_bits = 0)
+                         const double* d_expected, double mixture, hipStream_t ready_stream, int64_t* ticket, int slab_bits = 0,
+                         const double* d_mix = nullptr)
 {
   if (n <= 0 || n > c->slab) return ed_fail(ED_ERR_INVALID, "ed_cohort_submit: %lld samples in a slab of %lld", (long long)n, (long long)c->slab);
   if ((d_phi == nullptr) != (d_expected == nullptr)) return ed_fail(ED_ERR_INVALID, "ed_cohort_submit: phi and expected go together");
@@ -656,6 +662,7 @@ static int cohort_submit(ed_cohort* c, const int32_t* d_test, const int32_t* d_r
   }
   if (int rc = cohort_adopt(c, b)) return rc;
   if (slab_bits) b->counts_bits = slab_bits;
+  b->d_mix = d_mix;   // (before batch_prepare below: the constants of this slab are made from it wherever they are made)
   const bool pipelined = c->pipelined();
   hipStream_t main_st = c->mains[sl.lane];                    // the slab's lane: its emission stream and its fit stream
   hipStream_t fit_st = pipelined ? c->fits[sl.lane] : main_st;
@@ -708,7 +715,7 @@ static int cohort_submit(ed_cohort* c, const int32_t* d_test, const int32_t* d_r
   }
   if (c->phi_bins > 1) {
     if (int rc = batch_run_bins_skip(b, d_test, d_ref, c->phi_bins, sl.d_phib, sl.d_edges, sl.d_exp, mixture, main_st)) return rc;
-    sl.bins_pending = true; sl.last_test = d_test; sl.last_ref = d_ref; sl.last_mix = mixture;
+    sl.bins_pending = true; sl.last_test = d_test; sl.last_ref = d_ref; sl.last_mix = mixture; sl.last_mix_s = d_mix;
   } else {
     const int rc = ed_batch_run(b, d_test, d_ref, sl.d_phi, sl.d_exp, mixture, main_st);
     b->src_phi = b->src_exp = nullptr;
@@ -729,6 +736,14 @@ try {
   return cohort_submit(c, d_test, d_ref, n_samples, d_phi, d_expected, mixture, (hipStream_t)ready_stream, ticket);
 }
 ED_CATCH("ed_cohort_submit")
+
+ED_EXPORT int ed_cohort_submit_mix(ed_cohort* c, const int32_t* d_test, const int32_t* d_ref, int64_t n_samples, const double* d_phi,
+                                   const double* d_expected, const double* d_mixture, void* ready_stream, int64_t* ticket)
+try {
+  if (!c || !d_test || !d_ref || !d_mixture) return ed_fail(ED_ERR_INVALID, "ed_cohort_submit_mix: NULL argument");
+  return cohort_submit(c, d_test, d_ref, n_samples, d_phi, d_expected, 1.0, (hipStream_t)ready_stream, ticket, 0, d_mixture);
+}
+ED_CATCH("ed_cohort_submit_mix")
 
 static int cohort_slot_of(ed_cohort* c, int64_t ticket, ed_cohort::Slot** out)
 {
@@ -902,9 +917,10 @@ static int cohort_host_buffers(ed_cohort* c, ed_cohort::Slot& sl, bool need_raw)
 
 // One slab from host memory: both matrices through the copy stream, then cohort_submit.  The slot's device buffers are
 // reused: the caller must have collected the results of ticket - slabs_in_flight (its decoration reads the counts).
-ED_EXPORT int ed_cohort_submit_host(ed_cohort* c, const void* test, const void* ref, int64_t n_samples, int layout, int wire,
-                                    int64_t row_stride, const double* phi, const double* expected, double mixture, int64_t* ticket)
-try {
+static int cohort_submit_host(ed_cohort* c, const void* test, const void* ref, int64_t n_samples, int layout, int wire,
+                              int64_t row_stride, const double* phi, const double* expected, double mixture, int64_t* ticket,
+                              const double* d_mix)
+{
   if (!c || !test || !ref) return ed_fail(ED_ERR_INVALID, "ed_cohort_submit_host: NULL argument");
   if ((layout != 0 && layout != 1) || (wire != 4 && wire != 2)) return ed_fail(ED_ERR_INVALID, "ed_cohort_submit_host: layout 0 / 1, wire 4 / 2");
   if (n_samples <= 0 || n_samples > c->slab) return ed_fail(ED_ERR_INVALID, "ed_cohort_submit_host: %lld samples in a slab of %lld", (long long)n_samples, (long long)c->slab);
@@ -933,14 +949,20 @@ try {
       if (!wide) { if (int rc = stager_upload_narrow(c->stager, (const int32_t*)ref, count, (uint16_t*)sl.own_ref, c->copy, &wide)) return rc; }
       if (wide) ++c->n_wide_slabs;
     } else wide = true;                  // (pinned int32: the DMA engine reads it in place -- no host pass to narrow in)
-    if (!wide) return cohort_submit(c, sl.own_test, sl.own_ref, n_samples, phi, expected, mixture, c->copy, ticket, 16);
+    if (!wide) return cohort_submit(c, sl.own_test, sl.own_ref, n_samples, phi, expected, mixture, c->copy, ticket, 16, d_mix);
   }
   // both matrices onto the link first, then their device passes: the DMA engine is not left waiting behind a kernel
   if (int rc = cohort_upload_matrix(c, sl, test, n_samples, layout, wire, row_stride, 0, sl.own_test, 1)) return rc;
   if (int rc = cohort_upload_matrix(c, sl, ref, n_samples, layout, wire, row_stride, 1, sl.own_ref, 1)) return rc;
   if (int rc = cohort_upload_matrix(c, sl, test, n_samples, layout, wire, row_stride, 0, sl.own_test, 2)) return rc;
   if (int rc = cohort_upload_matrix(c, sl, ref, n_samples, layout, wire, row_stride, 1, sl.own_ref, 2)) return rc;
-  return cohort_submit(c, sl.own_test, sl.own_ref, n_samples, phi, expected, mixture, c->copy, ticket, 32);
+  return cohort_submit(c, sl.own_test, sl.own_ref, n_samples, phi, expected, mixture, c->copy, ticket, 32, d_mix);
+}
+
+ED_EXPORT int ed_cohort_submit_host(ed_cohort* c, const void* test, const void* ref, int64_t n_samples, int layout, int wire,
+                                    int64_t row_stride, const double* phi, const double* expected, double mixture, int64_t* ticket)
+try {
+  return cohort_submit_host(c, test, ref, n_samples, layout, wire, row_stride, phi, expected, mixture, ticket, nullptr);
 }
 ED_CATCH("ed_cohort_submit_host")
 
@@ -1048,8 +1070,8 @@ static int cohort_collect(ed_cohort* c, int64_t ticket, int64_t sample0, int64_t
 struct ed_slab_seg { int64_t slab, row0, row1; };
 template <class NEXT>
 static int cohort_run_host_slabs(ed_cohort* c, const void* test, const void* ref, int64_t S_total, NEXT next_slab, int layout, int wire,
-                                 const double* phi, const double* expected, double mixture, double* phi_out, double* expected_out,
-                                 uint8_t* path_out, int64_t* n_calls, std::vector<ed_slab_seg>* segs)
+                                 const double* phi, const double* expected, double mixture, const double* mix_host, double* phi_out,
+                                 double* expected_out, uint8_t* path_out, int64_t* n_calls, std::vector<ed_slab_seg>* segs)
 {
   if (!c || !test || !ref || S_total <= 0) return ed_fail(ED_ERR_INVALID, "ed_cohort_run_host: bad arguments");
   if ((phi == nullptr) != (expected == nullptr)) return ed_fail(ED_ERR_INVALID, "ed_cohort_run_host: phi and expected go together");
@@ -1080,6 +1102,16 @@ static int cohort_run_host_slabs(ed_cohort* c, const void* test, const void* ref
       }
       HIP_TRY(hipMemcpyAsync(c->d_par, phi, (size_t)S_total * 8, hipMemcpyHostToDevice, c->copy));
       HIP_TRY(hipMemcpyAsync(c->d_par + S_total, expected, (size_t)S_total * 8, hipMemcpyHostToDevice, c->copy));
+      HIP_TRY(hipStreamSynchronize(c->copy));
+    }
+    // per-sample mixtures: the same way, complete on the device before any slab's constants kernel, on whichever stream that runs
+    if (mix_host) {
+      if (c->mixv_cap < S_total) {
+        if (c->d_mixv) { HIP_TRY(hipFree(c->d_mixv)); c->d_mixv = nullptr; c->mixv_cap = 0; }
+        HIP_TRY(hipMalloc((void**)&c->d_mixv, (size_t)S_total * 8));
+        c->mixv_cap = S_total;
+      }
+      HIP_TRY(hipMemcpyAsync(c->d_mixv, mix_host, (size_t)S_total * 8, hipMemcpyHostToDevice, c->copy));
       HIP_TRY(hipStreamSynchronize(c->copy));
     }
     started = true;
@@ -1115,8 +1147,9 @@ static int cohort_run_host_slabs(ed_cohort* c, const void* test, const void* ref
     }
     const size_t off = (layout == 1) ? (size_t)s0 * E * wire : (size_t)s0 * wire;
     int64_t tk = -1;
-    if (int rc = ed_cohort_submit_host(c, (const char*)test + off, (const char*)ref + off, n, layout, wire, S_total,
-                                       phi ? c->d_par + s0 : nullptr, phi ? c->d_par + S_total + s0 : nullptr, mixture, &tk))
+    if (int rc = cohort_submit_host(c, (const char*)test + off, (const char*)ref + off, n, layout, wire, S_total,
+                                    phi ? c->d_par + s0 : nullptr, phi ? c->d_par + S_total + s0 : nullptr, mixture, &tk,
+                                    mix_host ? c->d_mixv + s0 : nullptr))
       return rc;
     flight.push_back({tk, i});
   }
@@ -1133,9 +1166,33 @@ try {
   const int64_t n_slabs = (S_total + c->slab - 1) / c->slab;
   int64_t i = 0;
   auto next = [&]() -> int64_t { return i < n_slabs ? i++ : -1; };
-  return cohort_run_host_slabs(c, test, ref, S_total, next, layout, wire, phi, expected, mixture, phi_out, expected_out, path_out, n_calls, nullptr);
+  return cohort_run_host_slabs(c, test, ref, S_total, next, layout, wire, phi, expected, mixture, nullptr, phi_out, expected_out, path_out, n_calls,
+                               nullptr);
 }
 ED_CATCH("ed_cohort_run_host")
+
+// host mixtures [n]: every one finite (ed_cohort_run_host_mix, ed_multi_run_host_mix) -- checked before anything is uploaded or launched
+static int check_host_mixtures(const double* mixture, int64_t n, const char* who)
+{
+  if (!mixture) return ed_fail(ED_ERR_INVALID, "%s: NULL mixture", who);
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(mixture[i])) return ed_fail(ED_ERR_INVALID, "%s: mixture of sample %lld is not a finite number", who, (long long)i);
+  return ED_OK;
+}
+
+ED_EXPORT int ed_cohort_run_host_mix(ed_cohort* c, const void* test, const void* ref, int64_t S_total, int layout, int wire,
+                                     const double* phi, const double* expected, const double* mixture, double* phi_out, double* expected_out,
+                                     uint8_t* path_out, int64_t* n_calls)
+try {
+  if (!c || S_total <= 0) return ed_fail(ED_ERR_INVALID, "ed_cohort_run_host_mix: bad arguments");
+  if (int rc = check_host_mixtures(mixture, S_total, "ed_cohort_run_host_mix")) return rc;
+  const int64_t n_slabs = (S_total + c->slab - 1) / c->slab;
+  int64_t i = 0;
+  auto next = [&]() -> int64_t { return i < n_slabs ? i++ : -1; };
+  return cohort_run_host_slabs(c, test, ref, S_total, next, layout, wire, phi, expected, 1.0, mixture, phi_out, expected_out, path_out, n_calls,
+                               nullptr);
+}
+ED_CATCH("ed_cohort_run_host_mix")
 
 ED_EXPORT int ed_cohort_copy_calls(ed_cohort* c, ed_call* calls, ed_call_info* info, int64_t cap)
 try {

@@ -170,7 +170,7 @@ __device__ __forceinline__ double cov_expected(const double* __restrict__ X, int
 __global__ void k_sample_consts(const double* __restrict__ phi, const double* __restrict__ expected, double mixture,
                                 int64_t S, double* __restrict__ consts, int* __restrict__ cflags, unsigned long long* __restrict__ z_nerr,
                                 unsigned long long* __restrict__ z_tacc, unsigned int* __restrict__ z_notab, unsigned int* __restrict__ z_cold_n,
-                                int n_cold_n, double* __restrict__ phi_copy, double* __restrict__ exp_copy)
+                                int n_cold_n, double* __restrict__ phi_copy, double* __restrict__ exp_copy, const double* __restrict__ mix_s)
 {
   // phi_copy / exp_copy (cohort pipeline, parameters given by the caller): the slot's own copy of the slab's (phi, expected) -- what
   // the accessors and the call decoration read later -- written here instead of by two device-to-device copies on the emission stream
@@ -184,7 +184,7 @@ __global__ void k_sample_consts(const double* __restrict__ phi, const double* __
   if (phi_copy) { phi_copy[s] = phi[s]; exp_copy[s] = e; }
   const double sd = __builtin_sqrt((phi[s] * e) * (1. - e));
   double ep[3];
-  state_props(e, mixture, ep);
+  state_props(e, mix_s ? mix_s[s] : mixture, ep);   // mix_s: one mixture per sample (ed_batch_set_mixture)
 #pragma unroll
   for (int st = 0; st < 3; ++st) {
     double a1, a2;
@@ -605,7 +605,8 @@ constexpr int kVerifyRun = 8;
 __global__ void __launch_bounds__(kEmitBlock)
 k_emit_verify(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, const double* __restrict__ phi,
               const double* __restrict__ expected, double mixture, int64_t E, int64_t S, const double* __restrict__ loglik,
-              unsigned long long* __restrict__ counters, ed_emit_mismatch* __restrict__ first, int64_t cap, int64_t ce, int64_t cs)
+              unsigned long long* __restrict__ counters, ed_emit_mismatch* __restrict__ first, int64_t cap, int64_t ce, int64_t cs,
+              const double* __restrict__ mix_s)
 {
   const int64_t s_raw = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
   const int64_t e0 = (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * (kEmitBlock / 64) + (threadIdx.x >> 6)) * kVerifyRun;
@@ -614,7 +615,7 @@ k_emit_verify(const int32_t* __restrict__ test, const int32_t* __restrict__ ref,
   const double ex = expected[s];
   const double sd = __builtin_sqrt((phi[s] * ex) * (1. - ex));
   double ep[3];
-  state_props(ex, mixture, ep);
+  state_props(ex, mix_s ? mix_s[s] : mixture, ep);
   int bad = 0, ncell = 0;
 #pragma unroll 1
   for (int st = 0; st < 3; ++st) {
@@ -1769,6 +1770,8 @@ struct ed_batch {
   const double* prepared_phi = nullptr; // ... from these parameters
   const double* prepared_exp = nullptr;
   double prepared_mix = 0.0;
+  const double* prepared_mix_s = nullptr;
+  const double* d_mix = nullptr;        // ed_batch_set_mixture: DEVICE double [S], one mixture per sample (NULL: the runs' scalar)
   double split_frac = 0.0;
   hipEvent_t split_ev = nullptr;
   bool split_recorded = false;          // the last run recorded split_ev
@@ -2424,13 +2427,14 @@ __global__ void k_emit_bins(const int32_t* __restrict__ test, const int32_t* __r
                             const double* __restrict__ phib, const double* __restrict__ expected, const double* __restrict__ X, int K,
                             const double* __restrict__ beta, double mixture, int64_t E, int64_t S, double* __restrict__ loglik,
                             unsigned long long* __restrict__ nerr, const double* __restrict__ ctab, int rtab, const uint8_t* __restrict__ left_out,
-                            const int* __restrict__ skip, int tiles_per_wg, int64_t n_blk);
+                            const int* __restrict__ skip, int tiles_per_wg, int64_t n_blk, const double* __restrict__ mix_s);
 __global__ void k_bins_ctab(int B, const double* __restrict__ edges, const double* __restrict__ phib, const double* __restrict__ expected,
-                            double mixture, int64_t S, int rtab, double* __restrict__ ctab, const int* __restrict__ skip);
+                            double mixture, int64_t S, int rtab, double* __restrict__ ctab, const int* __restrict__ skip,
+                            const double* __restrict__ mix_s);
 __global__ void k_emit_bins_tab(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, int B, const double* __restrict__ edges,
                                 const double* __restrict__ phib, const double* __restrict__ expected, double mixture, int64_t E, int64_t S,
                                 const double* __restrict__ ctab, int rtab, double* __restrict__ loglik, uint8_t* __restrict__ left_out,
-                                const int* __restrict__ skip, int64_t blk0, int64_t nblk);
+                                const int* __restrict__ skip, int64_t blk0, int64_t nblk, const double* __restrict__ mix_s);
 constexpr int kBinsRtab = 8192;    // reference counts covered by the table of the depth-binned model's constants (edbins.inc)
 }
 
@@ -2602,7 +2606,7 @@ static int batch_prepare(ed_batch* b, const double* d_phi, const double* d_expec
                      b->d_consts, b->d_cflags,
                      zero_counters ? b->d_nerr : (unsigned long long*)nullptr, b->emit_mode >= 1 ? b->d_tacc : (unsigned long long*)nullptr,
                      b->emit_mode >= 1 ? b->d_notab : (unsigned int*)nullptr, b->emit_mode >= 1 ? b->d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
-                     from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr);
+                     from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr, b->d_mix);
   b->src_phi = b->src_exp = nullptr;
   b->prepared_zeroed = zero_counters;
   if (b->emit_mode >= 1) { if (int rc = tab_build(b, d_test, d_ref, st)) return rc; }
@@ -2610,7 +2614,7 @@ static int batch_prepare(ed_batch* b, const double* d_phi, const double* d_expec
   hipLaunchKernelGGL(k_emit_tables, dim3((unsigned)((S + 63) / 64), (unsigned)(kEmitTab / 4), 3), dim3(256), 0, st, b->d_consts, S, b->d_tab_gl,
                      b->d_tab_lg);
   HIP_TRY(hipGetLastError());
-  b->prepared = true; b->prepared_phi = d_phi; b->prepared_exp = d_expected; b->prepared_mix = mixture;
+  b->prepared = true; b->prepared_phi = d_phi; b->prepared_exp = d_expected; b->prepared_mix = mixture; b->prepared_mix_s = b->d_mix;
   return ED_OK;
 }
 
@@ -2645,7 +2649,10 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
   b->last_test = d_test; b->last_ref = d_ref; b->last_expected = d_expected; b->last_layout = b->counts_layout; b->last_cb = cb;
   struct SrcClear { ed_batch* b; ~SrcClear() { b->src_phi = b->src_exp = nullptr; } } src_clear{b};   // (whatever path the run takes)
   b->last_cov_X = em.cov ? em.X : nullptr; b->last_cov_K = em.cov ? em.K : -1; b->last_cov_beta = em.cov ? em.beta : nullptr;
-  const bool ready = plain && b->prepared && b->prepared_phi == d_phi && b->prepared_exp == d_expected && b->prepared_mix == mixture && !b->fused;
+  // (the preparation is made by the same submission right before this run -- b->prepared is cleared below -- so a caller that rewrites the
+  // per-sample mixtures behind the same pointer between two runs always gets fresh constants)
+  const bool ready = plain && b->prepared && b->prepared_phi == d_phi && b->prepared_exp == d_expected && b->prepared_mix == mixture &&
+                     b->prepared_mix_s == b->d_mix && !b->fused;
   b->prepared = false;
   if (!plain || (ready && !b->prepared_zeroed)) HIP_TRY(hipMemsetAsync(b->d_nerr, 0, 64, st));     // (otherwise: k_sample_consts, below or in batch_prepare)
   b->prepared_zeroed = false;
@@ -2656,7 +2663,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
     hipLaunchKernelGGL(k_sample_consts, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, from_src ? b->src_phi : d_phi, from_src ? b->src_exp : d_expected, mixture, S,
                        b->d_consts, b->d_cflags, b->d_nerr, tabm ? b->d_tacc : (unsigned long long*)nullptr, tabm ? b->d_notab : (unsigned int*)nullptr,
                        tabm ? b->d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
-                       from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr);
+                       from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr, b->d_mix);
     if (tabm) { if (int rc = tab_build(b, d_test, d_ref, st)) return rc; }
     else if (!b->fused)
       hipLaunchKernelGGL(k_emit_tables, dim3((unsigned)((S + 63) / 64), (unsigned)(kEmitTab / 4), 3), dim3(256), 0, st, b->d_consts, S,
@@ -2758,7 +2765,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
             }
           }
           hipLaunchKernelGGL(k_bins_ctab, dim3((unsigned)((S + 63) / 64), (unsigned)(kBinsRtab / 4)), dim3(256), 0, st, bins, d_edges, d_phi, d_expected,
-                             mixture, S, kBinsRtab, b->d_ctab, em.skip);
+                             mixture, S, kBinsRtab, b->d_ctab, em.skip, b->d_mix);
           // In the cohort pipeline the launch is cut into pieces: the NEXT slab's fit consists of several kernels whose workgroups need a
           // (nearly) whole CU each, and such a workgroup only gets one at a launch boundary, where the CUs drain -- under one uncut
           // launch the 3.5-ms fit took the launch's whole 13.8 ms and then stood between two emission launches.
@@ -2768,7 +2775,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
             if (pn <= 0) continue;
             const dim3 pgrid((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(pn, 65535), (unsigned)((pn + 65534) / 65535));
             hipLaunchKernelGGL(k_emit_bins_tab, pgrid, dim3(kEmitBlock), 0, st, d_test, d_ref, bins, d_edges, d_phi, d_expected, mixture, E, S,
-                               b->d_ctab, kBinsRtab, b->d_loglik, b->d_left_out, em.skip, pb0, pn);
+                               b->d_ctab, kBinsRtab, b->d_loglik, b->d_left_out, em.skip, pb0, pn, b->d_mix);
           }
           ctab = b->d_ctab;
         }
@@ -2779,7 +2786,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
           hipLaunchKernelGGL(k_emit_bins, fgrid,
                              dim3(kEmitBlock), 0, st, d_test, d_ref, bins, d_edges, d_phi, em.cov ? (const double*)nullptr : d_expected, em.X,
                              em.cov ? em.K : -1, em.beta, mixture, E, S, b->d_loglik,
-                             b->d_nerr, ctab, kBinsRtab, b->d_left_out, em.skip, tpw, eblk);
+                             b->d_nerr, ctab, kBinsRtab, b->d_left_out, em.skip, tpw, eblk, b->d_mix);
         }
       }
       emit_launch(head, blk0);
@@ -2867,6 +2874,17 @@ try {
   return batch_run_impl(b, d_test, d_ref, d_phi, d_expected, mixture, stream_, EmitModel());
 }
 ED_CATCH("ed_batch_run")
+
+// one mixture per sample (matched tumour / normal pairs, each at its own tumour fraction): read by the kernels that turn (phi, expected,
+// mixture) into shape parameters -- k_sample_consts and the per-cell kernels of the depth-binned / covariate models and of the self-checks
+ED_EXPORT int ed_batch_set_mixture(ed_batch* b, const double* d_mixture)
+try {
+  if (!b) return ed_fail(ED_ERR_INVALID, "ed_batch_set_mixture: NULL batch");
+  b->d_mix = d_mixture;
+  b->prepared = false;
+  return ED_OK;
+}
+ED_CATCH("ed_batch_set_mixture")
 
 // workspace of the column-wise beta-binomial fit (shared by ed_batch_fit and ed_select_reference_set)
 struct FitWork {
@@ -3370,7 +3388,7 @@ try {
   const int64_t eblk = (E + rows_per_block - 1) / rows_per_block;
   hipLaunchKernelGGL(k_emit_verify, dim3((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(eblk, 65535), (unsigned)((eblk + 65534) / 65535)),
                      dim3(kEmitBlock), 0, b->stream, d_test, d_ref, d_phi, d_expected, mixture, E, S, b->d_loglik,
-                     dcnt.as<unsigned long long>(), dfirst.as<ed_emit_mismatch>(), cap, b->counts_layout ? (int64_t)1 : S, b->counts_layout ? E : (int64_t)1);
+                     dcnt.as<unsigned long long>(), dfirst.as<ed_emit_mismatch>(), cap, b->counts_layout ? (int64_t)1 : S, b->counts_layout ? E : (int64_t)1, b->d_mix);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   unsigned long long c[3] = {0, 0, 0};
@@ -3405,7 +3423,8 @@ try {
   const int64_t eblk = (E + rows_per_block - 1) / rows_per_block;
   hipLaunchKernelGGL(k_emit_verify_tol, dim3((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(eblk, 65535), (unsigned)((eblk + 65534) / 65535)),
                      dim3(kEmitBlock), 0, b->stream, d_test, d_ref, d_phi, d_expected, mixture, E, S, b->d_loglik, rel_tol, abs_tol,
-                     dcnt.as<unsigned long long>(), dfirst.as<ed_emit_mismatch>(), cap, b->counts_layout ? (int64_t)1 : S, b->counts_layout ? E : (int64_t)1, b->counts_layout ? b->cb() : 4);
+                     dcnt.as<unsigned long long>(), dfirst.as<ed_emit_mismatch>(), cap, b->counts_layout ? (int64_t)1 : S, b->counts_layout ? E : (int64_t)1, b->counts_layout ? b->cb() : 4,
+                     b->d_mix);
   HIP_TRY(hipGetLastError());
   unsigned long long c[5] = {0, 0, 0, 0, 0};
   if (int rc = ed_d2h(c, dcnt.p, 40, b->stream)) return rc;

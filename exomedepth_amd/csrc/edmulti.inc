@@ -134,9 +134,10 @@ ED_CATCH("ed_multi_set_option")
 // of its pipeline is free, so a device that is slower -- or busy with somebody else's work -- takes fewer slabs instead of setting the wall time with a
 // fixed share (round 5 dealt contiguous shares).  Which device served a slab does not show in the results: every slab is fitted and called on its own, and
 // the call table is put together in slab order = column order.
-ED_EXPORT int ed_multi_run_host(ed_multi* m, const void* test, const void* ref, int64_t S_total, int layout, int wire, const double* phi,
-                                const double* expected, double mixture, double* phi_out, double* expected_out, uint8_t* path_out, int64_t* n_calls)
-try {
+static int multi_run_host(ed_multi* m, const void* test, const void* ref, int64_t S_total, int layout, int wire, const double* phi,
+                          const double* expected, double mixture, const double* mix_host, double* phi_out, double* expected_out, uint8_t* path_out,
+                          int64_t* n_calls)
+{
   if (!m || !test || !ref || S_total <= 0) return ed_fail(ED_ERR_INVALID, "ed_multi_run_host: bad arguments");
   const int64_t D = (int64_t)m->devs.size(), n_slabs = (S_total + m->slab - 1) / m->slab;
   m->S_total = S_total;
@@ -154,7 +155,8 @@ try {
         return i;
       };
       int64_t k = 0;
-      d->rc = cohort_run_host_slabs(d->cohort, test, ref, S_total, next, layout, wire, phi, expected, mixture, phi_out, expected_out, path_out, &k, &d->segs);
+      d->rc = cohort_run_host_slabs(d->cohort, test, ref, S_total, next, layout, wire, phi, expected, mixture, mix_host, phi_out, expected_out, path_out,
+                                    &k, &d->segs);
     } catch (...) { d->rc = ed_caught("ed_multi_run_host"); }     // (nothing may leave a thread's function)
     if (d->rc != ED_OK) {
       queue.store(n_slabs, std::memory_order_relaxed);             // the others stop taking slabs: the run has failed
@@ -187,7 +189,24 @@ try {
   if (n_calls) *n_calls = (int64_t)m->calls.size();
   return ED_OK;
 }
+
+ED_EXPORT int ed_multi_run_host(ed_multi* m, const void* test, const void* ref, int64_t S_total, int layout, int wire, const double* phi,
+                                const double* expected, double mixture, double* phi_out, double* expected_out, uint8_t* path_out, int64_t* n_calls)
+try {
+  return multi_run_host(m, test, ref, S_total, layout, wire, phi, expected, mixture, nullptr, phi_out, expected_out, path_out, n_calls);
+}
 ED_CATCH("ed_multi_run_host")
+
+// every device's pipeline uploads the whole mixture vector once and its slabs take their windows of it (as for given phi / expected)
+ED_EXPORT int ed_multi_run_host_mix(ed_multi* m, const void* test, const void* ref, int64_t S_total, int layout, int wire, const double* phi,
+                                    const double* expected, const double* mixture, double* phi_out, double* expected_out, uint8_t* path_out,
+                                    int64_t* n_calls)
+try {
+  if (!m || !test || !ref || S_total <= 0) return ed_fail(ED_ERR_INVALID, "ed_multi_run_host_mix: bad arguments");
+  if (int rc = check_host_mixtures(mixture, S_total, "ed_multi_run_host_mix")) return rc;
+  return multi_run_host(m, test, ref, S_total, layout, wire, phi, expected, 1.0, mixture, phi_out, expected_out, path_out, n_calls);
+}
+ED_CATCH("ed_multi_run_host_mix")
 
 ED_EXPORT int ed_multi_copy_calls(ed_multi* m, ed_call* calls, ed_call_info* info, int64_t cap)
 try {

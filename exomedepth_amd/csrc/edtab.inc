@@ -1157,7 +1157,7 @@ __global__ void __launch_bounds__(kEmitBlock)
 k_emit_verify_tol(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, const double* __restrict__ phi,
                   const double* __restrict__ expected, double mixture, int64_t E, int64_t S, const double* __restrict__ loglik,
                   double rel_tol, double abs_tol, unsigned long long* __restrict__ counters, ed_emit_mismatch* __restrict__ first,
-                  int64_t cap, int64_t ce, int64_t cs, int cb)
+                  int64_t cap, int64_t ce, int64_t cs, int cb, const double* __restrict__ mix_s)
 {
   const int64_t s_raw = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
   const int64_t e0 = (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * (kEmitBlock / 64) + (threadIdx.x >> 6)) * kVerifyRun;
@@ -1166,7 +1166,7 @@ k_emit_verify_tol(const int32_t* __restrict__ test, const int32_t* __restrict__ 
   const double ex = expected[s];
   const double sd = __builtin_sqrt((phi[s] * ex) * (1. - ex));
   double ep[3];
-  state_props(ex, mixture, ep);
+  state_props(ex, mix_s ? mix_s[s] : mixture, ep);
   int bad = 0, ncell = 0;
   double max_rel = 0.0, max_abs = 0.0;
 #pragma unroll 1

@@ -212,6 +212,15 @@ int ed_batch_expected_cov(ed_batch* batch, const double* d_X, int n_cov, const d
 int ed_batch_run(ed_batch* batch, const int32_t* d_test, const int32_t* d_ref, const double* d_phi,
                  const double* d_expected, double mixture, void* stream);
 
+/* One mixture per sample: matched tumour / normal pairs, each at its own tumour fraction (the reference's somatic.CNV.call,
+ * R/class_definition.R:442-461, runs one pair at a time with a scalar prop.tumor).  d_mixture: DEVICE double [n_samples], or NULL to
+ * turn it off.  While it is set, ed_batch_run, ed_batch_run_bins, ed_batch_run_cov, ed_batch_verify_emissions and
+ * ed_batch_verify_emissions_tol read sample s's mixture from d_mixture[s] and IGNORE their scalar `mixture` argument; fused mode and
+ * every emit mode are served.  The array is read by the kernels of each run (not copied): keep it alive and unchanged until the run's
+ * results have been read.  Sample s then gives exactly what it gives through the scalar path with mixture = d_mixture[s], bit for bit,
+ * whatever the other samples' values.  The dispersion fits do not see the mixture (the reference's fit ignores prop.tumor). */
+int ed_batch_set_mixture(ed_batch* batch, const double* d_mixture);
+
 /* Execution mode of ed_batch_run.
  *   fused = 0 (default)  two kernels: emissions into the [n_exons][3][n_samples] likelihood matrix, then Viterbi,
  *                        overlapped by chromosome groups on two streams -- the fastest path today;
@@ -541,6 +550,11 @@ int ed_cohort_set_option(ed_cohort* cohort, const char* name, double value);
  * slabs have been submitted; its counts must stay valid until then too (the call decoration reads them). */
 int ed_cohort_submit(ed_cohort* cohort, const int32_t* d_test, const int32_t* d_ref, int64_t n_samples, const double* d_phi,
                      const double* d_expected, double mixture, void* ready_stream, int64_t* ticket);
+/* ed_cohort_submit with one mixture per sample of the slab: d_mixture DEVICE double [n_samples] (ed_batch_set_mixture for the slab's
+ * batch), produced -- like the counts -- by work on ready_stream or complete when this is called, and kept valid until the ticket has
+ * been waited for (a depth-binned slab done again reads it then).  A later ed_cohort_submit of the same slot runs with its scalar again. */
+int ed_cohort_submit_mix(ed_cohort* cohort, const int32_t* d_test, const int32_t* d_ref, int64_t n_samples, const double* d_phi,
+                         const double* d_expected, const double* d_mixture, void* ready_stream, int64_t* ticket);
 /* The batch object holding a ticket's results -- read them with the ed_batch_* accessors (ed_batch_n_calls, ed_batch_copy_*,
  * ed_batch_path, ...), which wait for that slab only -- and the DEVICE arrays of its (phi, expected).  ED_ERR_STATE once the
  * ticket's slot has been reused. */
@@ -598,6 +612,13 @@ int ed_host_free(void* hptr);
 int ed_cohort_run_host(ed_cohort* cohort, const void* test, const void* ref, int64_t n_total, int layout, int wire,
                        const double* phi, const double* expected, double mixture, double* phi_out, double* expected_out,
                        uint8_t* path_out, int64_t* n_calls);
+/* ed_cohort_run_host for matched tumour / normal pairs (test = tumour, ref = normal), each at its own tumour fraction: `mixture` is a
+ * HOST double [n_total] indexed by the cohort's column, uploaded once as given phi / expected are.  Column s gives exactly what
+ * ed_cohort_run_host gives for it with the scalar mixture[s] (likelihoods, path, calls, decoration), whatever the slab width and the
+ * other columns' values.  A value that is not a finite number: ED_ERR_INVALID before anything is uploaded or launched. */
+int ed_cohort_run_host_mix(ed_cohort* cohort, const void* test, const void* ref, int64_t n_total, int layout, int wire,
+                           const double* phi, const double* expected, const double* mixture, double* phi_out, double* expected_out,
+                           uint8_t* path_out, int64_t* n_calls);
 int ed_cohort_copy_calls(ed_cohort* cohort, ed_call* calls, ed_call_info* info, int64_t cap);
 int ed_cohort_run_status(ed_cohort* cohort, int64_t* n_unconverged, int64_t* n_gsl_errors);
 /* table-driven emit modes: ed_batch_table_stats summed over the slabs of the last ed_cohort_run_host */
@@ -631,6 +652,11 @@ int ed_multi_n_devices(const ed_multi* multi);
 int ed_multi_set_option(ed_multi* multi, const char* name, double value);
 int ed_multi_run_host(ed_multi* multi, const void* test, const void* ref, int64_t n_total, int layout, int wire, const double* phi,
                       const double* expected, double mixture, double* phi_out, double* expected_out, uint8_t* path_out, int64_t* n_calls);
+/* ed_cohort_run_host_mix over every device: HOST mixture [n_total], one per column; the results do not depend on the number of devices
+ * or on which device served a slab, as for ed_multi_run_host.  Non-finite values: ED_ERR_INVALID before any device work. */
+int ed_multi_run_host_mix(ed_multi* multi, const void* test, const void* ref, int64_t n_total, int layout, int wire, const double* phi,
+                          const double* expected, const double* mixture, double* phi_out, double* expected_out, uint8_t* path_out,
+                          int64_t* n_calls);
 int ed_multi_copy_calls(ed_multi* multi, ed_call* calls, ed_call_info* info, int64_t cap);
 int ed_multi_run_status(ed_multi* multi, int64_t* n_unconverged, int64_t* n_gsl_errors);
 int ed_multi_table_status(ed_multi* multi, int64_t out[4]);

@@ -51,6 +51,47 @@ CallCNVs.cohort <- function(counts, chromosome, start, end, name, transition.pro
        reference.choice = rs$choice, n.chosen = rs$n.chosen, n.unconverged = r$n.unconverged)
 }
 
+## somatic.CNV.call (R/class_definition.R:442-461) for a cohort of matched tumour / normal pairs, each pair at its own tumour fraction:
+## per pair new('ExomeDepth', test = tumor, reference = normal, prop.tumor = prop.tumor) + CallCNVs(transition.probability = 1e-4).
+##   normal, tumor  integer matrices, exons x pairs; column j of tumor is matched with column j of normal (columns named by pair)
+##   prop.tumor     one value for every pair, or one value per pair
+##   emit.mode, devices, slab  as CallCNVs.cohort
+## Returns the list of CallCNVs.cohort (calls with one row per CNV call, sample = the pair's column name) without the reference-set fields.
+somatic.CNV.call.cohort <- function(normal, tumor, prop.tumor = 1, chromosome, start, end, names, emit.mode = 2L, devices = NULL,
+                                    slab = 256L) {
+  message('Warning: this function is largely untested and experimental')                   # R/class_definition.R:444
+  if (!identical(dim(normal), dim(tumor))) stop('normal and tumor must be matrices of the same shape (exons x pairs)')
+  if (length(prop.tumor) != 1 && length(prop.tumor) != ncol(tumor))
+    stop('prop.tumor must have length 1 or one value per sample')
+  if (length(start) != length(chromosome) || length(end) != length(chromosome) || length(names) != length(chromosome))
+    stop('Chromosome, name, start and end vector must have the same lengths.\n')          # R/class_definition.R:319
+  if (nrow(tumor) != length(chromosome)) stop('The annotation vectors must have the same length as the rows of counts')
+  message('Initializing the exomeDepth object')                                            # :445
+  ## exon order of CallCNVs (R/class_definition.R:322-327), as in CallCNVs.cohort
+  chr <- as.character(chromosome)
+  chr.names.used <- unique(chr)
+  chr.levels <- c(as.character(seq(1, 22)), chr.names.used[!chr.names.used %in% as.character(seq(1, 22))])
+  chr.levels <- chr.levels[chr.levels %in% chr.names.used]
+  o <- order(factor(chr, levels = chr.levels), 0.5 * (start + end))
+  tumor <- tumor[o, , drop = FALSE]; normal <- normal[o, , drop = FALSE]
+  chr <- chr[o]; start <- start[o]; end <- end[o]; names <- names[o]
+  storage.mode(tumor) <- "integer"; storage.mode(normal) <- "integer"
+  chrom.off <- as.integer(c(0L, cumsum(table(factor(chr, levels = chr.levels)))))
+  message('Now calling the CNVs')                                                          # :451
+  r <- .Call("ed_call_cnvs_batch", tumor, normal, chrom.off, as.integer(start), as.integer(end),
+             as.double(1e-4), as.double(50000), NULL, NULL, as.double(prop.tumor), as.integer(slab), 0L,
+             0L, 1L, as.integer(emit.mode), if (is.null(devices)) NULL else as.integer(devices), PACKAGE = "ExomeDepth")
+  calls <- data.frame(sample = colnames(tumor)[r$sample], start.p = r$start.p, end.p = r$end.p,
+                      type = c("deletion", "duplication")[r$type], nexons = r$nexons,       # R/class_definition.R:385
+                      start = start[r$start.p], end = end[r$end.p], chromosome = chr[r$start.p],  # :379-381
+                      BF = r$BF, reads.expected = r$reads.expected, reads.observed = r$reads.observed,
+                      reads.ratio = r$reads.ratio, stringsAsFactors = FALSE)
+  calls$id <- paste('chr', calls$chromosome, ':', calls$start, '-', calls$end, sep = '')        # :383
+  calls$id <- gsub(pattern = "chrchr", replacement = "chr", calls$id)                           # :384
+  list(calls = calls, phi = r$phi, expected = r$expected, phi.bins = r$phi.bins, complete.bins = r$complete.bins,
+       n.unconverged = r$n.unconverged)
+}
+
 ## What stands where new('ExomeDepth') calls aod::betabin (R/class_definition.R:118-119, :168), for every column at once.
 ## fit.mode 0: maximum likelihood; 1: aod's procedure (Nelder-Mead from the glm start) -- a point inside optim()'s
 ## tolerance region, not pinned against aod itself.  Returns list(phi, expected, converged).

@@ -21,6 +21,7 @@
 #include <R.h>
 #include <Rinternals.h>
 #include <R_ext/Rdynload.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -113,7 +114,9 @@ static void edr_guard_release(SEXP p)
  *   start, end        integer[n_exons]
  *   tprob, ecl        transition.probability, expected.CNV.length (:261)
  *   phi, expected     double[n_samples] or NULL (fitted on the device: fit_mode 0 = maximum likelihood, 1 = aod-nm)
- *   prop_tumor        the mixture (:86, :189)            slab     samples per slab of the pipeline (integer)
+ *   prop_tumor        the mixture (:86, :189): length 1, or one value per sample -- matched tumour / normal pairs (test = tumour,
+ *                     reference = normal, somatic.CNV.call at :442-461), each at its own tumour fraction
+ *   slab              samples per slab of the pipeline (integer)
  *   want_path         integer 0/1: also return the Viterbi state of every exon (raw n_exons x n_samples)
  *   phi_bins          the reference's phi.bins (R/class_definition.R:86, :120-147): 1 = one dispersion per sample; 2..8 = one per depth
  *                     level of the reference counts, phi.linear interpolated per exon (phi / expected cannot be given then)
@@ -141,8 +144,18 @@ SEXP edr_call_cnvs_batch(SEXP test, SEXP reference, SEXP chrom_off, SEXP start, 
     Rf_error("phi and expected must both be given, one value per sample");
   if (B < 1 || B > 8) Rf_error("phi.bins must be in 1..8");
   if (B > 1 && given) Rf_error("with phi.bins > 1 the dispersions are fitted per depth level: phi and expected cannot be given");
-  const double mix = REAL(prop_tumor)[0];
-  if (mix != 1) Rprintf("As a warning (this could be normal), the mixture coefficient is %f\n", mix);   /* src/CNV_estimate.cpp:61 */
+  const R_xlen_t n_mix = XLENGTH(prop_tumor);
+  const int per_sample = (n_mix == S && S != 1);
+  if (n_mix != 1 && !per_sample) Rf_error("prop.tumor must have length 1 or one value per sample");
+  const double *mixv = REAL(prop_tumor);
+  if (per_sample)
+    for (R_xlen_t i = 0; i < n_mix; i++)
+      if (!isfinite(mixv[i])) Rf_error("prop.tumor must have length 1 or one value per sample");
+  const double mix = mixv[0];
+  /* src/CNV_estimate.cpp:61, once per get_loglike_matrix call: once per sample whose value is not 1, in column order, for one value
+   * per sample (the reference's loop of somatic.CNV.call) */
+  for (R_xlen_t i = 0; i < n_mix; i++)
+    if (mixv[i] != 1) Rprintf("As a warning (this could be normal), the mixture coefficient is %f\n", mixv[i]);
   /* the plan and the cohort live in an external pointer with a finalizer from before the first R allocation on: an R error raised
    * inside an allocation below (a longjmp out of this function) leaves them to the garbage collector instead of leaking device memory */
   int nprot = 0;
@@ -176,8 +189,12 @@ SEXP edr_call_cnvs_batch(SEXP test, SEXP reference, SEXP chrom_off, SEXP start, 
     SEXP rexp = PROTECT(allocVector(REALSXP, S)); nprot++;
     SEXP rpath = R_NilValue;
     if (INTEGER(want_path)[0]) { rpath = PROTECT(allocMatrix(RAWSXP, E, S)); nprot++; }
-    rc = ed_multi_run_host(co, INTEGER(test), INTEGER(reference), S, 1 /* R's column-major */, 4, given ? REAL(phi) : NULL,
-                            given ? REAL(expected) : NULL, mix, REAL(rphi), REAL(rexp), rpath != R_NilValue ? RAW(rpath) : NULL, &n);
+    if (per_sample)
+      rc = ed_multi_run_host_mix(co, INTEGER(test), INTEGER(reference), S, 1 /* R's column-major */, 4, given ? REAL(phi) : NULL,
+                                 given ? REAL(expected) : NULL, mixv, REAL(rphi), REAL(rexp), rpath != R_NilValue ? RAW(rpath) : NULL, &n);
+    else
+      rc = ed_multi_run_host(co, INTEGER(test), INTEGER(reference), S, 1 /* R's column-major */, 4, given ? REAL(phi) : NULL,
+                             given ? REAL(expected) : NULL, mix, REAL(rphi), REAL(rexp), rpath != R_NilValue ? RAW(rpath) : NULL, &n);
     if (rc == ED_OK) {
       ed_call *calls = (ed_call *) R_alloc((size_t)(n > 0 ? n : 1), sizeof(ed_call));
       ed_call_info *info = (ed_call_info *) R_alloc((size_t)(n > 0 ? n : 1), sizeof(ed_call_info));
