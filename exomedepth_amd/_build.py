@@ -65,23 +65,7 @@ def build(force=False, verbose=False):
 
 
 # Diagnostic variants of the library (same sources, different code generation); never loaded by the package itself.
-VARIANTS = {"coldinline": ["-DED_COLD_INLINE"],
-            # the library with its experiment knobs (environment variables ED_TAB_REACH, ED_TAB_TW, ED_VIT_WAVES, ED_SM_NSPLIT, ED_COHORT_*) enabled
-            "knobs": ["-DED_EXPERIMENT_KNOBS"],
-            # k_viterbi_sm without its raised wave priority (round 5 A/B: tools/ab.sh vitprio0)
-            "vitprio0": ["-DED_VITSM_PRIO=0"], "prepprio3": ["-DED_PREP_PRIO=3"], "prio_prep_over_vit": ["-DED_VITSM_PRIO=0", "-DED_PREP_PRIO=3"], "vitdepth1": ["-DED_VITSM_DEPTH=1"], "fitpre4": ["-DED_FIT_PRE=4"], "tabbuild256": ["-DED_TAB_BUILD_THREADS=256"],
-            # (the "xu16" timing build -- k_emit_tab_sm reading its counts as if 16 bits wide, profiles/r05_u16_experiment.txt -- became the real thing:
-            #  ed_batch_set_counts_bits(batch, 16))
-            # timing experiments on k_emit_tab_sm (wrong results by construction): without its stores / LDS look-ups / global look-ups
-            "xnostore": ["-DED_SM_X_NOSTORE"], "xnolds": ["-DED_SM_X_NOLDS"], "xnoglobal": ["-DED_SM_X_NOGLOBAL"],
-            "xnoldsglobal": ["-DED_SM_X_NOLDS", "-DED_SM_X_NOGLOBAL"],
-            "tabper8": ["-DED_TAB_PER=8"],
-            # round 1's Horner step (coefficient as an "s" asm operand): contains the VALU-write-SGPR -> VALU-read hazard
-            # (tools/isa_hazard_scan.py); built only to demonstrate it on hardware next to the fixed library
-            "sgprasm": ["-DED_PM_FMA_K_SGPR_OPERAND"],
-            # k_fit_hist of the shallow geometry with 4 samples per workgroup: half the LDS, emission workgroups fit beside it
-            "fitlight": ["-DED_HG8_WG=4"],
-            # every automatic variable starts from a bit pattern (0xAA...) instead of whatever the register or stack slot held: a read of an uninitialised
+VARIANTS = {# every automatic variable starts from a bit pattern (0xAA...) instead of whatever the register or stack slot held: a read of an uninitialised
             # variable shows up as a wrong (and reproducible) result instead of a run-to-run difference -- host and device code
             "autoinit": ["-ftrivial-auto-var-init=pattern"],
             # k_fit_hnewton's per-cell path with the short digamma series (irreproducible fits), alone and with pattern-initialised variables
@@ -91,13 +75,7 @@ VARIANTS = {"coldinline": ["-DED_COLD_INLINE"],
             # (no -shared-libsan: the runtime is whatever tools/sanitize.sh preloads -- gcc's stock libasan / libtsan; ROCm's own
             # ASan runtime intercepts hsa_amd_memory_pool_allocate for DEVICE instrumentation and fails on a plain process)
             "asan": ["-fsanitize=address,undefined", "-fno-sanitize=vptr,function", "-fno-gpu-sanitize", "-g", "-fno-omit-frame-pointer", "-Wl,--unresolved-symbols=ignore-all"],
-            "tsan": ["-fsanitize=thread", "-fno-gpu-sanitize", "-g", "-fno-omit-frame-pointer", "-Wl,--unresolved-symbols=ignore-all"],
-            # k_emit_tab_sm experiments: plain loads / stores; 512-thread workgroups with half the LDS (two per CU)
-            "smplain": ["-DED_SM_NT=0"], "smntld": ["-DED_SM_NT=1"], "smntst": ["-DED_SM_NT=2"],
-            "sm512": ["-DED_SM_THREADS=512", "-DED_SM_ENTRIES=3072"],
-            # ... 8- and 12-wave workgroups with the whole table window (one per CU, registers left on every SIMD for a Viterbi / table-build wave)
-            "nofence": ["-DED_X_NO_NULL_FENCE"], "sm512full": ["-DED_SM_THREADS=512"], "sm768full": ["-DED_SM_THREADS=768"],
-            "smmask": ["-DED_SM_MASKED=1"], "sm6784": ["-DED_SM_ENTRIES=6784"], "smmask6784": ["-DED_SM_MASKED=1", "-DED_SM_ENTRIES=6784"], "sm4096": ["-DED_SM_ENTRIES=4096"], "sm3584": ["-DED_SM_ENTRIES=3584"], "sm5120": ["-DED_SM_ENTRIES=5120"]}
+            "tsan": ["-fsanitize=thread", "-fno-gpu-sanitize", "-g", "-fno-omit-frame-pointer", "-Wl,--unresolved-symbols=ignore-all"]}
 
 
 def variant_path(name):

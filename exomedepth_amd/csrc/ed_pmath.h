@@ -198,16 +198,7 @@ ED_PM_FN double ed_pm_fma(double a, double b, double c) { return __builtin_fma(a
  * tests/test_isa_hazards.py keep the compiler's output free of it).  Here nothing but SALU ever writes s[28:29]
  * (caller-saved in the AMDGPU calling convention, so out-of-line callees need not preserve them), and an SALU write
  * followed by a VALU read is interlocked by the hardware. */
-#if defined(__HIP_DEVICE_COMPILE__) && defined(ED_PM_FMA_K_SGPR_OPERAND)
-/* DIAGNOSTIC VARIANT ONLY (libedcore_sgprasm.so, tools/soak_emission.py --variant sgprasm): round 1's form, kept so that the
- * hazard can be shown on hardware against the fixed library.  Never part of the product build. */
-__device__ static __inline__ __attribute__((always_inline)) double ed_pm_fma_k(double a, double b, double k)
-{
-  double d;
-  __asm__("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(k));
-  return d;
-}
-#elif defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 __device__ static __inline__ __attribute__((always_inline)) double ed_pm_fma_k(double a, double b, double k)
 {
   double d;

@@ -17,13 +17,8 @@
 #include "ed_sing_tables.h"
 
 // Cold functions (ranges the path rarely or never reaches) are kept out of line so that the hot routes stay small.
-// -DED_COLD_INLINE builds the diagnostic variant of the library in which they are inlined instead
-// (tools/soak_emission.py --variant coldinline: same bits expected, different code generation).
-#if defined(ED_COLD_INLINE)
-#define EDSF_COLD __forceinline__
-#else
+// (A build with them inlined soaked without a mismatch: profiles/r02_soak_coldinline.json, r03_z_soak_coldinline.json.)
 #define EDSF_COLD __noinline__
-#endif
 
 namespace edsf {
 

@@ -384,7 +384,6 @@ struct ed_cohort {
   hipStream_t mains[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr}, fits[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
   hipStream_t copy = nullptr;
   bool pipelined() const { return n_slots / n_lanes >= 2; }     // a lane with two or more slots overlaps the stages of its consecutive slabs
-  std::vector<hipStream_t> spare;
   int64_t next_ticket = 0;
   bool started = false;
   bool timing = false;
@@ -442,7 +441,6 @@ static void cohort_free(ed_cohort* c)
     if (c->fits[l]) (void)hipStreamDestroy(c->fits[l]);
   }
   if (c->copy) (void)hipStreamDestroy(c->copy);
-  for (hipStream_t s : c->spare) (void)hipStreamDestroy(s);
   delete c;
 }
 
@@ -456,8 +454,6 @@ try {
   if (!c) return ed_fail(ED_ERR_NOMEM, "out of host memory");
   c->plan = plan; c->slab = slab_samples; c->n_slots = slabs_in_flight;
   c->slots.resize((size_t)slabs_in_flight);
-  if (const char* e = ed_knob("ED_COHORT_OWN_QUEUES")) c->own_queues = atoi(e) != 0;
-  if (const char* e = ed_knob("ED_COHORT_SPLIT")) c->split_frac = atof(e);
   *cohort = c;
   return ED_OK;
 }
@@ -545,9 +541,6 @@ static int cohort_start(ed_cohort* c)
   c->n_lanes = c->lanes_opt > 0 ? c->lanes_opt : ((c->n_slots >= 4 && c->n_slots % 2 == 0) ? std::min(c->n_slots / 2, (int)ed_cohort::kMaxLanes) : 1);   // (0: the automatic rule)
   if (c->n_slots % c->n_lanes) c->n_lanes = 1;
   const bool pipelined = c->pipelined();
-  if (const char* e = ed_knob("ED_COHORT_SPARE_QUEUES")) {   // (diagnostic) hardware queues created, and left idle, ahead of the pipeline's
-    for (int i = 0; i < atoi(e) && i < 16; ++i) { hipStream_t sp; HIP_TRY(ed_stream_create(&sp, true, dev)); c->spare.push_back(sp); }
-  }
   // (every resource is made only if it is not there yet: a start that failed half-way -- device memory -- is taken up where it stopped by the next
   // submission instead of making the streams, batch objects and buffers it already has a second time)
   for (int l = 0; l < c->n_lanes; ++l) {
@@ -555,12 +548,10 @@ static int cohort_start(ed_cohort* c)
     if (pipelined && !c->fits[l]) HIP_TRY(ed_stream_create(&c->fits[l], c->own_queues, dev));
   }
   for (size_t i = 0; i < c->slots.size(); ++i) c->slots[i].lane = (int)(i % (size_t)c->n_lanes);
-  const char* so = ed_knob("ED_COHORT_SIDES_OWN");
-  const bool sides_own = c->own_queues && (so ? atoi(so) != 0 : true);
   for (auto& sl : c->slots) {
     if (!sl.batch) {
       if (int rc = ed_batch_create(&sl.batch, c->plan, c->slab)) return rc;
-      if (sides_own && !sl.batch->sides.empty()) {   // the stream the chains run on (single-group mode uses the first side stream only)
+      if (c->own_queues && !sl.batch->sides.empty()) {   // the stream the chains run on (single-group mode uses the first side stream only)
         hipStream_t own = nullptr;
         HIP_TRY(ed_stream_create(&own, true, dev));
         (void)hipStreamDestroy(sl.batch->sides[0]);

@@ -55,19 +55,6 @@
 // ------------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-// Experiment knobs (table reach / tile width, waves of the persistent Viterbi grid, shares per sample of the emission launch, the cohort
-// pipeline's queue layout) are read from the environment only in builds made with -DED_EXPERIMENT_KNOBS (exomedepth_amd/_build.py variant
-// "knobs"): the shipped library's behaviour does not depend on the caller's environment.
-static const char* ed_knob(const char* name)
-{
-#ifdef ED_EXPERIMENT_KNOBS
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
 static int ed_fail(int code, const char* fmt, ...)
 {
   char buf[512];
@@ -84,11 +71,7 @@ static int ed_fail(int code, const char* fmt, ...)
 // started from poisoned partial sums (tests/test_gpu_cohort.py, six slabs in flight, own_queues = 0, torch's HIP runtime in the process: results equal
 // to 1e-15 instead of bit for bit) -- the workspace's all-ones fill landed after the first pass had written its sums.  Every one-time initialisation by
 // hipMemset is therefore followed by this fence before the buffer is handed to a stream.
-#ifdef ED_X_NO_NULL_FENCE      // (diagnostic build only)
-static hipError_t ed_null_stream_fence() { return hipSuccess; }
-#else
 static hipError_t ed_null_stream_fence() { return hipStreamSynchronize(nullptr); }
-#endif
 
 // No C++ exception leaves the library: the callers are C (R's .Call, ctypes).  Every int-returning entry point is a function-try-block
 // closed by ED_CATCH, which turns what was thrown (in practice std::bad_alloc from a host container, std::system_error from a
@@ -729,10 +712,7 @@ __device__ __forceinline__ unsigned vit_step_q(double& v, double e, double t0, d
 // Register budget: a Viterbi wave shares its SIMD with emission waves (96 registers each; ed_batch_run overlaps
 // the two kernels), so its own allocation decides how many of them stay resident beside it: 154 registers
 // (no scratch) leave room for three.  Measured on MI355X: a 128-register build (four) is no faster.
-#ifndef ED_VIT_OCC
-#define ED_VIT_OCC 3
-#endif
-__global__ void __launch_bounds__(kWave, ED_VIT_OCC)
+__global__ void __launch_bounds__(kWave, 3)
 k_viterbi(const double* __restrict__ loglik, const double* __restrict__ lt4, double c0, double c1,
           const int32_t* __restrict__ chrom_off, const int64_t* __restrict__ word_off, int64_t S, int32_t C,
           uint32_t* __restrict__ bpq, uint8_t* __restrict__ last, const int32_t* __restrict__ job_off,
@@ -1390,12 +1370,6 @@ __global__ void k_fit_skip_prefixes(const double* __restrict__ eta, int* __restr
   skip_from[j] = from;
 }
 
-#ifndef ED_FIT_PACK_EARLY
-#define ED_FIT_PACK_EARLY 1
-#endif
-#ifndef ED_FIT_PRE
-#define ED_FIT_PRE 8      // cells of a column requested ahead of the one being consumed (round 5: 4 -> 8)
-#endif
 __global__ void __launch_bounds__(kWave * kFitSub)
 k_fit_accum(const int32_t* __restrict__ test, int64_t trs, int64_t tcs, const int32_t* __restrict__ ref, int64_t rrs,
             int64_t E, int64_t S, int stride, const double* __restrict__ eta, const double* __restrict__ lam, const int* __restrict__ done,
@@ -1422,7 +1396,7 @@ k_fit_accum(const int32_t* __restrict__ test, int64_t trs, int64_t tcs, const in
   // (trs, tcs) = (S, 1): one test column per sample; (1, 0): one shared test column.
   // The counts of the next kPre cells are requested before the current ones are consumed: ~150 VALU
   // instructions per cell do not cover an HBM round trip on their own.
-  constexpr int kPre = ED_FIT_PRE;
+  constexpr int kPre = 8;      // cells of a column requested ahead of the one being consumed (round 5: 4 -> 8)
   int yb[kPre], rb[kPre];
 #pragma unroll
   for (int k = 0; k < kPre; ++k) {
@@ -1621,12 +1595,8 @@ __device__ __forceinline__ bool fit_hist_runs(int depth, int launched, int mine)
 
 namespace hg8 {
 #define ED_HG_KS 8
-#ifdef ED_HG8_WG
-#define ED_HG_WG ED_HG8_WG
-#endif
 #include "edfit_hist.inc"
 #undef ED_HG_KS
-#undef ED_HG_WG
 }
 namespace hg4 {
 #define ED_HG_KS 4
@@ -1799,7 +1769,6 @@ struct ed_batch {
   int counts_layout = 0;         // 0: count matrices [E][S] (sample-minor); 1: [S][E] (sample-major, R's column-major E x S matrix) --
                                  // ed_batch_set_counts_layout; layout 1 serves the histogram fit and emit mode 2
   int emit_mode = 0;             // 0: strict (GSL's arithmetic operation for operation), 1: log-gamma difference tables
-  int tab_tw = 16;               // samples per tile of k_emit_tab (16 / 32 / 64)
   int tab_capY = 4096, tab_capR = 32768;   // longest obs / ref table of a sample (entries); the tot table has their sum
   double tab_reach = 8.0;        // a table covers this multiple of the sample's mean count (+ 64)
   int tab_tails = 1;             // emit mode 2: samples whose counts outgrow the LDS windows are served by Stirling's series beyond them (ed_batch_set_emit_tails)
@@ -2439,8 +2408,6 @@ constexpr int kBinsRtab = 8192;    // reference counts covered by the table of t
 }
 
 // ---- table-driven emission mode (edtab.inc): buffers, segment table, the per-run table build ----
-static int64_t tab_rows_per_wg(int tw) { return 4 * (64 / tw); }
-
 static void tab_release(ed_batch* b)
 {
   void** ptrs[] = {(void**)&b->d_tabs, (void**)&b->d_tdims, (void**)&b->d_notab, (void**)&b->d_tacc, (void**)&b->d_cold_list, (void**)&b->d_cold_n, (void**)&b->d_seg_t,
@@ -2456,14 +2423,14 @@ static int tab_setup(ed_batch* b)
   const ed_plan* p = b->plan;
   const int64_t S = b->S, E = p->E;
   b->tab_stride = 2 * ((int64_t)b->tab_capY + b->tab_capR);
-  if ((int64_t)b->tab_tw * b->tab_stride * 24 >= ((int64_t)1 << 31))
-    return ed_fail(ED_ERR_INVALID, "emit mode 1: %d samples x %lld table entries x 24 bytes per tile exceed 2^31 (smaller table caps or tile width)",
-                   b->tab_tw, (long long)b->tab_stride);
+  if ((int64_t)kTabTw * b->tab_stride * 24 >= ((int64_t)1 << 31))
+    return ed_fail(ED_ERR_INVALID, "emit mode 1: %d samples x %lld table entries x 24 bytes per tile exceed 2^31 (smaller table caps)",
+                   kTabTw, (long long)b->tab_stride);
   // (a sixteenth of the cells: the lists of round 5 -- a thirty-second -- ran out at 1 600 reads per exon, where 2 % of the cells lie beyond the conditioning limit,
   //  and the strict pass then walked all 2 x 10^8 cells again: 7.6 ms)
   b->cold_cap = (unsigned int)std::min<int64_t>(std::max<int64_t>(E * S / 16, 1 << 16), (int64_t)1 << 28) / kColdLists * kColdLists;
-  // segments in job order, workgroups numbered for k_emit_tab's tile (rows x tab_tw samples), as ed_batch_create does for k_emit_batch
-  const int64_t rows = tab_rows_per_wg(b->tab_tw), nsb = (S + b->tab_tw - 1) / b->tab_tw;
+  // segments in job order, workgroups numbered for k_emit_tab's tile (rows x kTabTw samples), as ed_batch_create does for k_emit_batch
+  const int64_t rows = 4 * (64 / kTabTw), nsb = (S + kTabTw - 1) / kTabTw;
   int64_t blk = 0;
   b->seg_t.clear();
   for (auto& jb : b->jobs) {
@@ -2533,7 +2500,6 @@ static int tab_setup_sm(ed_batch* b)
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0) b->vit_waves = prop.multiProcessorCount * 4;
-    if (const char* e = ed_knob("ED_VIT_WAVES")) { if (atoi(e) > 0) b->vit_waves = atoi(e); }      // (experiments: profiles/r05_viterbi_waves.txt)
   }
   if (ok && hipMemset(b->d_loglik_sm, 0, ((size_t)S * 3 * b->Epad + 512) * 8) != hipSuccess) ok = false;
   if (ok && hipMemcpy(b->d_blk_sm, bm.data(), bm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ok = false;
@@ -2577,12 +2543,12 @@ static int tab_build(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, h
   else if (E > 0)
     hipLaunchKernelGGL(k_tab_stats, dim3((unsigned)((S + 63) / 64), (unsigned)((E + 64 * step - 1) / (64 * step))), dim3(256), 0, st, d_test, d_ref, E, S,
                        step, b->d_tacc);
-  if (S < 256 && ED_TAB_BUILD_THREADS == 64)
+  if (S < 256)
     hipLaunchKernelGGL(k_tab_build<256>, dim3((unsigned)S, 3), dim3(256), 0, st, b->d_consts, b->d_cflags, b->d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
                        b->d_tdims, S, b->d_tabs, b->tab_stride, b->d_notab, tails, b->d_twins, b->d_tlg0);
   else
-    hipLaunchKernelGGL(k_tab_build<ED_TAB_BUILD_THREADS>, dim3((unsigned)S, 3), dim3(ED_TAB_BUILD_THREADS), 0, st, b->d_consts, b->d_cflags, b->d_tacc, b->tab_reach,
-                       b->tab_capY, b->tab_capR, b->d_tdims, S, b->d_tabs, b->tab_stride, b->d_notab, tails, b->d_twins, b->d_tlg0);
+    hipLaunchKernelGGL(k_tab_build<64>, dim3((unsigned)S, 3), dim3(64), 0, st, b->d_consts, b->d_cflags, b->d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
+                       b->d_tdims, S, b->d_tabs, b->tab_stride, b->d_notab, tails, b->d_twins, b->d_tlg0);
   HIP_TRY(hipGetLastError());
   return ED_OK;
 }
@@ -2687,7 +2653,6 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
     }
     if (tabsm) {    // n, base: blocks of 64 exons; every sample gets nsplit workgroups that share them
       int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(16, (512 + S - 1) / S));
-      if (const char* e = ed_knob("ED_SM_NSPLIT")) { if (atoi(e) > 0) nsplit = atoi(e); }
       nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(nsplit, n / 32));
       const int64_t nwg = ((S + 7) / 8) * 8 * nsplit;
       if (cl1 && cb == 2)
@@ -2700,12 +2665,8 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
                            b->d_consts);
       return;
     }
-    const uint32_t nsb = (uint32_t)((S + b->tab_tw - 1) / b->tab_tw);
-#define ED_TAB_LAUNCH(TW)                                                                                                                \
-    hipLaunchKernelGGL(k_emit_tab<TW>, dim3((unsigned)n), dim3(kTabBlock), 0, st, d_test, d_ref, b->d_tdims, b->d_tabs, b->tab_stride, b->d_seg_t, \
-                       b->n_jobs, base, S, nsb, b->d_loglik, b->d_cold_list, b->d_cold_n, b->cold_cap)
-    if (b->tab_tw == 64) ED_TAB_LAUNCH(64); else if (b->tab_tw == 32) ED_TAB_LAUNCH(32); else if (b->tab_tw == 8) ED_TAB_LAUNCH(8); else if (b->tab_tw == 4) ED_TAB_LAUNCH(4); else ED_TAB_LAUNCH(16);
-#undef ED_TAB_LAUNCH
+    hipLaunchKernelGGL(k_emit_tab<kTabTw>, dim3((unsigned)n), dim3(kTabBlock), 0, st, d_test, d_ref, b->d_tdims, b->d_tabs, b->tab_stride, b->d_seg_t,
+                       b->n_jobs, base, S, (uint32_t)((S + kTabTw - 1) / kTabTw), b->d_loglik, b->d_cold_list, b->d_cold_n, b->cold_cap);
   };
   if (b->timing) HIP_TRY(hipEventRecord(b->ev[1], st));
   const int64_t cells = E * S;
@@ -2973,10 +2934,7 @@ static void fitwork_free(FitWork* w)
 // pass met only barely (its step IS ~1e-6 from the stride-16 start): a fourth pass over most of the cohort reference sets' 32 768 columns,
 // 1.5 of the leg's 9 ms, confirmed what was already there.
 constexpr double kFitStepTol = 2e-5;
-#ifndef ED_FIT_COARSE
-#define ED_FIT_COARSE 4
-#endif
-constexpr int kFitCoarsePasses = ED_FIT_COARSE;   // Newton steps on every 16th exon before the full passes (1 / 16 of a full pass each)
+constexpr int kFitCoarsePasses = 4;   // Newton steps on every 16th exon before the full passes (1 / 16 of a full pass each)
 // use_hist: build count histograms once and iterate on them in one launch (needs one test column per sample laid
 // out like the reference counts: tcs == 1, trs == rrs); otherwise per-cell passes, one launch pair per pass.
 static int fit_columns(FitWork& w, const int32_t* d_test, int64_t trs, int64_t tcs, const int32_t* d_ref, int64_t rrs,
@@ -3060,7 +3018,7 @@ static int fit_columns(FitWork& w, const int32_t* d_test, int64_t trs, int64_t t
   // start then (round 6), and again before each of the first full passes as columns converge.  Which slot a column takes does not show in its sums:
   // k_fit_accum picks its digamma series per lane, and k_fit_update reduces a slot's partials in chunk order (tests/test_gpu_fit_invariance.py).
   const bool can_pack = S >= 4096 && w.colmap;
-  const bool pack_early = can_pack && skip_K > 0 && tmod > 0 && d_skip_from && ED_FIT_PACK_EARLY;
+  const bool pack_early = can_pack && skip_K > 0 && tmod > 0 && d_skip_from;
   auto compact = [&]() {
     (void)hipMemsetAsync(w.n_map, 0, 4, st);
     hipLaunchKernelGGL(k_fit_compact, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, w.done, S, w.colmap, w.n_map);
@@ -3191,8 +3149,6 @@ try {
   if (mode != 0 && mode != 1 && mode != 2) return ed_fail(ED_ERR_INVALID, "ed_batch_set_emit_mode: 0 (strict), 1 (tables, exon-major tiles) or 2 (tables, sample-major)");
   if (mode >= 1) {
     HIP_TRY(hipSetDevice(b->plan->device));
-    if (const char* e = ed_knob("ED_TAB_REACH")) { if (!b->d_tabs && atof(e) >= 1.0) b->tab_reach = atof(e); }   // (experiments)
-    if (const char* e = ed_knob("ED_TAB_TW")) { const int tw = atoi(e); if (!b->d_tabs && (tw == 4 || tw == 8 || tw == 16 || tw == 32 || tw == 64)) b->tab_tw = tw; }
     if (int rc = tab_setup(b)) return rc;
     if (mode == 2) { if (int rc = tab_setup_sm(b)) return rc; }
   }

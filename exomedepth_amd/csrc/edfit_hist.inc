@@ -6,11 +6,7 @@
 // depth points to (all three the first time); a device word set from THIS fit's data (k_fit_start: the largest
 // per-sample mean total) decides on the device which of the launched ones runs (fit_hist_runs): no host round trip.
 constexpr int kHistId = ED_HG_KS;                        // the geometry: 8, 4 or 2 = samples that share 147 KB worth of bins
-#ifdef ED_HG_WG
-constexpr int kHistSamples = ED_HG_WG;                   // samples per workgroup of k_fit_hist (<= kHistId: a smaller LDS footprint, other workgroups fit beside it)
-#else
-constexpr int kHistSamples = kHistId;
-#endif
+constexpr int kHistSamples = kHistId;                    // samples per workgroup of k_fit_hist
 constexpr int kHistKy = 1024 * 8 / kHistId;              // bins of the test count
 constexpr int kHistKr = 4096 * 8 / kHistId;              // bins of the reference count
 constexpr int kHistKn = 4096 * 8 / kHistId;              // bins of the total

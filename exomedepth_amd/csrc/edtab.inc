@@ -22,11 +22,9 @@
 // gather serves all three), T1 at entry 0 (Ly entries, index obs), T2 at Ly (Lr entries, index ref), T3 at Ly + Lr
 // (Ly + Lr entries, index tot); samples `stride` entries apart.
 
-#ifndef ED_PREP_PRIO
-#define ED_PREP_PRIO 0       // wave priority of a slab's preparation kernels (k_tab_stats_sm, k_tab_build), the emission stream's critical path: 3 against 0, with the
-                             // Viterbi kernel at 0 or 3, measured equal (4.08-4.18 / 4.04-4.13 / 4.08-4.24 ms per step) -- wave priority arbitrates issue slots, and these
-                             // kernels wait for memory and for each other's registers, not for issue slots
-#endif
+// A slab's preparation kernels (k_tab_stats_sm, k_tab_build) are the emission stream's critical path, yet run at the default wave priority: 3 against 0,
+// with the Viterbi kernel at 0 or 3, measured equal (4.08-4.18 / 4.04-4.13 / 4.08-4.24 ms per step) -- wave priority
+// arbitrates issue slots, and these kernels wait for memory and for each other's registers, not for issue slots.
 namespace {
 
 // Counts on the device: int32 (R's integers; cb = 4) or, in the sample-major table mode only (ed_batch_set_counts_bits(batch, 16)), uint16 (cb = 2: counts
@@ -86,9 +84,6 @@ __global__ void __launch_bounds__(64)
 k_tab_stats_sm(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, int64_t pitch, int64_t E, int64_t S, int step,
                unsigned long long* __restrict__ acc, int cb)
 {
-#if ED_PREP_PRIO
-  __builtin_amdgcn_s_setprio(ED_PREP_PRIO);
-#endif
   const int lane = threadIdx.x, wave = blockIdx.y;
   const int64_t s = blockIdx.x;
   unsigned long long sy = 0, sr = 0, n = 0;
@@ -170,10 +165,7 @@ __device__ __forceinline__ double tab_ref0_bound(double a12, double a2, double n
 // and term, whatever the count), and its cells are served up to the conditioning limit instead of up to a table length -- a branch of the emission kernel
 // (emit_tail_share, a branch of k_emit_tab_sm taken per workgroup) walks the tail samples.  Which samples are tail samples is decided from the same subsampled statistics as
 // the table lengths: by the data alone, not by the launch history.
-#ifndef ED_SM_ENTRIES
-#define ED_SM_ENTRIES 6144
-#endif
-constexpr int kSmEntries = ED_SM_ENTRIES;   // table entries a workgroup keeps in LDS (x 24 B = 147 456 B)
+constexpr int kSmEntries = 6144;          // table entries a workgroup keeps in LDS (x 24 B = 147 456 B)
 constexpr int kSmT1Max = 1024;            // ... at most this many of them from the obs table
 constexpr double kTailMeanOverWindow = 1.25;
 constexpr int kTailMaxCount = 1 << 24;    // tail samples: obs + ref below this (the limit of the conditioning search)
@@ -307,18 +299,12 @@ __device__ __forceinline__ ed_dd dd_shfl_up(ed_dd v, int d)
 // it; a running double-double carries the total from sweep to sweep.  (16 entries per thread: with 4 the scan -- 10 double-double
 // additions and 14 shuffles per thread and sweep -- cost three times the logarithms.)  The association of the additions differs
 // from the sequential definition's: to ~2^-100, i.e. the same entries after rounding.
-#ifndef ED_TAB_PER
-#define ED_TAB_PER 16
-#endif
-constexpr int kTabPer = ED_TAB_PER;
+constexpr int kTabPer = 16;
 // Workgroups of ONE wave (round 5; 256 threads before): the kernel runs next to k_viterbi_sm's persistent grid and the next slab's fit, and
 // a one-wave workgroup is placed wherever a SIMD has registers left, while a four-wave one waits for a CU with room on all four; the scan
 // across waves (an LDS step and a barrier per state and sweep) goes away with them.  A sweep now covers 64 x 16 = 1 024 entries.
 // (A batch of few samples has few tables to build and the chip to itself: there the four-wave form finishes the long tot table sooner --
 // tab_build launches it below 256 samples.)
-#ifndef ED_TAB_BUILD_THREADS
-#define ED_TAB_BUILD_THREADS 64
-#endif
 template <int kTabBuildBlock>
 __global__ void __launch_bounds__(kTabBuildBlock)
 k_tab_build(const double* __restrict__ consts, const int* __restrict__ cflags, const unsigned long long* __restrict__ acc, double reach, int capY,
@@ -326,9 +312,6 @@ k_tab_build(const double* __restrict__ consts, const int* __restrict__ cflags, c
             int tails = 0, int4* __restrict__ wins = nullptr, double* __restrict__ lg0 = nullptr)
 {
   constexpr int kTabBuildWaves = kTabBuildBlock / 64;
-#if ED_PREP_PRIO
-  __builtin_amdgcn_s_setprio(ED_PREP_PRIO);      // the next emission launch waits for this kernel; what it shares its SIMDs with (Viterbi, the fit) is waited for later
-#endif
   __shared__ double s_logt[ED_PM_LOGT_N * 3];
   __shared__ ed_dd wtot[3][kTabBuildWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -431,7 +414,8 @@ typedef unsigned int ed_v2u __attribute__((ext_vector_type(2)));
 // it, lane = (row, sample).  TW is what an XCD's L2 must hold the tables of (the workgroup numbering deals XCD x the sample
 // blocks x, x + 8, ... ONE at a time, as k_emit_batch does): 16 samples x ~0.3 MB of hot entries.  Counts and likelihood
 // rows are streamed with nontemporal hints so that they do not evict the tables.  Same segment / launch-range interface as
-// k_emit_batch (seg built for this tile shape: ed_batch::seg_t).
+// k_emit_batch (seg built for this tile shape: ed_batch::seg_t).  Launched with TW = kTabTw.
+constexpr int kTabTw = 16;
 template <int TW>
 __global__ void __launch_bounds__(kTabBlock)
 k_emit_tab(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, const int4* __restrict__ dims,
@@ -635,21 +619,10 @@ k_tab_cold(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, co
 //   loglik    f64   [S][3][Epad]      (k_viterbi_sm reads it through LDS transposition; the [E][3][S] form is made on request)
 // A workgroup (16 waves) owns one sample and a share of the launch's 64-exon blocks; a wave reads 64 consecutive exons
 // (256 B per matrix), looks its three entries up in LDS (or, beyond the LDS range, in the global tables: L2) and writes three
-// 512-byte rows.  Workgroup i runs on XCD i % 8: the shares of one sample sit on one XCD.
-#ifndef ED_SM_THREADS
-#define ED_SM_THREADS 1024
-#endif
-#ifndef ED_SM_ENTRIES
-#define ED_SM_ENTRIES 6144
-#endif
-#ifndef ED_SM_MASKED
-#define ED_SM_MASKED 1
-#endif
-#ifndef ED_SM_NT
-#define ED_SM_NT 3       // bit 0: nontemporal count loads, bit 1: nontemporal likelihood stores
-#endif
-// Round 4, what bounds this kernel (1.9 ms per 200 000 x 1024 launch, 3.5 TB/s of its 33 B/cell), from timing builds (_build.py
-// xnostore / xnolds / xnoglobal): without its stores 1.27 ms, without its LDS look-ups 1.94 (no change), without the look-ups in the
+// 512-byte rows.  Workgroup i runs on XCD i % 8: the shares of one sample sit on one XCD.  Counts are loaded and likelihoods
+// stored nontemporally.
+// Round 4, what bounds this kernel (1.9 ms per 200 000 x 1024 launch, 3.5 TB/s of its 33 B/cell), from timing builds that each left
+// one part out: without its stores 1.27 ms, without its LDS look-ups 1.94 (no change), without the look-ups in the
 // global tables 1.72.  So: not the LDS; the stores cost 0.66 ms; and the read side alone is slow -- a wave has one block of counts
 // (512 B) in flight, 8 KB per CU, ~1 TB/s at the loaded latency, and cannot have more: the vector-memory counter completes in order
 // and the loop holds operations that may or may not be issued (masked global look-ups, masked stores, the list's atomic), so before
@@ -664,7 +637,7 @@ k_tab_cold(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, co
 // nearly every wave and turn for the 10 % of the cells that are warm (ref or tot >= 2 476; 3 % at a window of 4 000 entries, which
 // the LDS cannot hold), cost what the pipeline gains.  None is kept: the look-ups beyond the resident windows are what this
 // kernel's time is made of once the stores are paid, and only tables that fit (shallower data, or smaller entries) remove them.
-constexpr int kSmBlock = ED_SM_THREADS;
+constexpr int kSmBlock = 1024;   // 16 waves: 8- and 12-wave workgroups were slower (profiles/r05_ab_sm_threads.txt)
 
 // A tail sample's share of a launch (see tab_windows above): the same walk as the table samples', but an index beyond its LDS window is served by
 // Stirling's series instead of a look-up in global memory -- no tables exist there -- and cells count as served up to the conditioning limit.  The
@@ -838,18 +811,9 @@ k_emit_tab_sm(const int32_t* __restrict__ test, const int32_t* __restrict__ ref,
   const int64_t row0 = s * E;
   auto ldc = [test, ref, row0](bool is_ref, int64_t e) {
     const int32_t* base = is_ref ? ref : test;
-    if (cb == 2) {
-      const uint16_t* h = reinterpret_cast<const uint16_t*>(base) + row0 + e;
-      return (int32_t)((ED_SM_NT & 1) ? __builtin_nontemporal_load(h) : *h);
-    }
-    const int32_t* q = base + row0 + e;
-    return (ED_SM_NT & 1) ? __builtin_nontemporal_load(q) : *q;
+    if (cb == 2) return (int32_t)__builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(base) + row0 + e);
+    return __builtin_nontemporal_load(base + row0 + e);
   };
-#ifdef ED_SM_X_NOSTORE   // (timing builds only, wrong results by construction: what the kernel costs without its stores / LDS look-ups / global look-ups)
-  auto stl = [](double v, double* q) { if (v == 1.2345e300) *q = v; };
-#else
-  auto stl = [](double v, double* q) { if (ED_SM_NT & 2) __builtin_nontemporal_store(v, q); else *q = v; };
-#endif
   int32_t obs_n = ldc(false, e_n), ref_n = ldc(true, e_n);
   // stage C's operands
   double v_p[3][3], g_p[3][3];
@@ -870,26 +834,13 @@ k_emit_tab_sm(const int32_t* __restrict__ test, const int32_t* __restrict__ ref,
       for (int t = 0; t < 3; ++t) {
         const bool inl = intab_c && idx[t] < nres[t];
         const int li = inl ? (lbase[t] + idx[t]) * 3 : 0;
-#ifdef ED_SM_X_NOLDS
-        v_c[t][0] = (double)li; v_c[t][1] = (double)(li + 1); v_c[t][2] = (double)(li + 2);
-#else
         v_c[t][0] = lds[li]; v_c[t][1] = lds[li + 1]; v_c[t][2] = lds[li + 2];
-#endif
         outl_c[t] = intab_c && !inl;
-#if ED_SM_MASKED
         g_c[t][0] = g_c[t][1] = g_c[t][2] = 0.0;
-#ifdef ED_SM_X_NOGLOBAL
-        if (outl_c[t] && idx[t] < 0) {
-#else
         if (outl_c[t]) {     // only the lanes that need it: the texture addresser's time goes with the active lanes
-#endif
           const double* q = T + (gbase[t] + idx[t]) * 3;
           g_c[t][0] = q[0]; g_c[t][1] = q[1]; g_c[t][2] = q[2];
         }
-#else
-        const double* q = T + (outl_c[t] ? (gbase[t] + idx[t]) * 3 : (int64_t)0);
-        g_c[t][0] = q[0]; g_c[t][1] = q[1]; g_c[t][2] = q[2];
-#endif
       }
       locate(b + kStep, e_n, live_n);
       obs_n = ldc(false, e_n);
@@ -912,7 +863,7 @@ k_emit_tab_sm(const int32_t* __restrict__ test, const int32_t* __restrict__ ref,
 #pragma unroll
         for (int st = 0; st < 3; ++st) {
           const double d1 = outl_p[0] ? g_p[0][st] : v_p[0][st], d2 = outl_p[1] ? g_p[1][st] : v_p[1][st], d3 = outl_p[2] ? g_p[2][st] : v_p[2][st];
-          stl(ed_dtab_combine(d1, d2, d3), lrow + (int64_t)st * Epad + e_p);
+          __builtin_nontemporal_store(ed_dtab_combine(d1, d2, d3), lrow + (int64_t)st * Epad + e_p);
         }
       }
     }
@@ -977,15 +928,6 @@ k_tab_rows_to_cols(const int32_t* __restrict__ in, int64_t E, int64_t n, int32_t
 // its own row back, two steps per ds_read_b128, as the ring slots are consumed.  Tile T + 3 is in flight from memory while
 // tile T + 2 is read from LDS and tiles T, T + 1 are in registers.  Loads run past the chromosome's end (into the next
 // chromosome's emissions or the next row; the matrix is padded): what is loaded there is never used.
-#ifndef ED_VITSM_OCC
-#define ED_VITSM_OCC 1
-#endif
-#ifndef ED_VITSM_PRIO
-#define ED_VITSM_PRIO 3
-#endif
-#ifndef ED_VITSM_DEPTH
-#define ED_VITSM_DEPTH 2     // 1 or 2
-#endif
 // Work distribution.  queue == nullptr: workgroup (x, y) = (sample group x, job job_base + y), as k_viterbi.  queue != nullptr (what
 // ed_batch_run launches): a PERSISTENT grid of `gridDim.x` waves -- one per SIMD of the chip -- pulls (job, sample group) items from
 // a counter, all groups of the longest chromosome first (the jobs are sorted by decreasing length: dynamic longest-processing-time).
@@ -995,7 +937,7 @@ k_tab_rows_to_cols(const int32_t* __restrict__ in, int64_t E, int64_t n, int32_t
 // kernel: the next slab's table build and fit, queued beside them, waited ~0.6 ms for the first chains to retire.  With one wave per
 // SIMD the makespan is the longest chromosome's chain (it cannot be less) and 261 registers per SIMD stay free for the neighbours.
 // queue[0]: next item; queue[1]: waves that have left -- the last one zeroes both for the next launch.
-__global__ void __launch_bounds__(kWave, ED_VITSM_OCC)
+__global__ void __launch_bounds__(kWave, 1)
 k_viterbi_sm(const double* __restrict__ loglik, int64_t Epad, const double* __restrict__ lt4, double c0, double c1,
              const int32_t* __restrict__ chrom_off, const int64_t* __restrict__ word_off, int64_t S, int32_t C,
              uint32_t* __restrict__ bpq, uint8_t* __restrict__ last, const int32_t* __restrict__ job_off,
@@ -1006,12 +948,10 @@ k_viterbi_sm(const double* __restrict__ loglik, int64_t Epad, const double* __re
   __shared__ double2 lds_lt[2][kVitTile][4];
   constexpr int kRowD = 18;                                   // doubles between rows in LDS (144 bytes)
   __shared__ __attribute__((aligned(16))) double lds_em[2][48 * kRowD];
-#if ED_VITSM_PRIO
   // The recurrence is one dependent chain per wave and the longest chromosome's chain IS the launch's makespan: a wave of another kernel
   // on the same SIMD (the next slab's table build and fit run beside this launch) that takes every other issue slot doubles it.  With a
   // raised priority the chain issues whenever it can and the neighbours get the slots its dependencies leave empty.
-  __builtin_amdgcn_s_setprio(ED_VITSM_PRIO);
-#endif
+  __builtin_amdgcn_s_setprio(3);
   for (;;) {
   unsigned int item = 0;
   if (queue) {
@@ -1065,13 +1005,13 @@ k_viterbi_sm(const double* __restrict__ loglik, int64_t Epad, const double* __re
   };
   constexpr int kRing = 2 * kVitTile;
   double er[kRing];
-  // staging registers of the cooperative loads: ED_VITSM_DEPTH sets in rotation.  With one set, tile t + 3 is requested at the top of
-  // tile t and parked at its end -- 16 steps = ~0.8 us later, less than a loaded HBM round trip, and with ONE wave per SIMD (the
-  // persistent grid) nobody else issues while it waits.  With two, tile t + 4 is requested at the top of tile t and parked at the end
-  // of tile t + 1: two tiles of cover.
-  v2d stgs[ED_VITSM_DEPTH][6];
+  // staging registers of the cooperative loads: two sets in rotation.  Tile t + 4 is requested at the top of tile t and parked at the
+  // end of tile t + 1: two tiles of cover.  (With one set, tile t + 3 was requested at the top of tile t and parked at its end -- 16
+  // steps = ~0.8 us later, less than a loaded HBM round trip, and with ONE wave per SIMD (the persistent grid) nobody else issues
+  // while it waits: profiles/r05_ab_vitdepth.txt.)
+  v2d stgs[2][6];
   double2 stl = ltw[lane];
-  // prologue: tiles 0 and 1 into the ring, tile 2 into LDS buffer 0, tile 3 (and 4) in flight at the top of tile 0
+  // prologue: tiles 0 and 1 into the ring, tile 2 into LDS buffer 0, tiles 3 and 4 in flight at the top of tile 0
   v2d (&stg)[6] = stgs[0];
   coop(0, stg); park(0, stg);
   coop(1, stg); park(1, stg);
@@ -1087,11 +1027,11 @@ k_viterbi_sm(const double* __restrict__ loglik, int64_t Epad, const double* __re
   (&lds_lt[0][0][0])[lane] = stl;
   __syncthreads();
   park(0, stg);
-  if (ED_VITSM_DEPTH > 1) coop(3, stgs[ED_VITSM_DEPTH - 1]);
+  coop(3, stgs[1]);
   auto tile = [&](auto par, int t, int nsteps, bool full) {
     constexpr int P = decltype(par)::value;
     stl = ltw[(t + 1) * 64 + lane];
-    if (ED_VITSM_DEPTH > 1) coop(t + 4, stgs[P]); else coop(t + 3, stgs[0]);
+    coop(t + 4, stgs[P]);
     uint32_t w = 0;
 #pragma unroll
     for (int g4 = 0; g4 < kVitTile / 4; ++g4) {
@@ -1114,7 +1054,7 @@ k_viterbi_sm(const double* __restrict__ loglik, int64_t Epad, const double* __re
     }
     *reinterpret_cast<uint32_t*>(bpb + (int64_t)t * wbytes + boff) = w;
     (&lds_lt[P ^ 1][0][0])[lane] = stl;
-    park(P ^ 1, ED_VITSM_DEPTH > 1 ? stgs[(P ^ 1) & (ED_VITSM_DEPTH - 1)] : stgs[0]);   // tile t + 3 -> the buffer tile t + 1 was read from during tile t - 1
+    park(P ^ 1, stgs[P ^ 1]);   // tile t + 3 -> the buffer tile t + 1 was read from during tile t - 1
     __syncthreads();
   };
   {

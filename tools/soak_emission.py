@@ -9,12 +9,11 @@ No host round trip, no CPU checker: ~4e9 cells/s, so 1e12 cells take minutes.  T
 the one unexplained fuzz event of round 1 (shape parameters a1, a2 < 10: phi 0.05-0.5; depth 1-10; S in {1, 3, 17, 70};
 batches created and destroyed between runs as the fuzzer does) and also covers ordinary exome depths.
 
-    python tools/soak_emission.py [--seconds 120] [--variant coldinline] [--seed 1] [--out gpurun_out/soak.json]
+    python tools/soak_emission.py [--seconds 120] [--variant autoinit] [--seed 1] [--out FILE]
     AMD_SERIALIZE_KERNEL=3 python tools/soak_emission.py ...        # every kernel serialised by the runtime
 
---variant coldinline loads exomedepth_amd/libedcore_coldinline.so (the cold special-function paths -- Gamma* below 10,
-log Gamma below 1/2 and in the Pade windows, the error path -- inlined instead of called: different code generation,
-same arithmetic).  On a mismatch the cells are printed, the case is saved under gpurun_out/ and the same inputs are run
+--variant NAME loads exomedepth_amd/libedcore_NAME.so, a diagnostic build of the same sources (exomedepth_amd/_build.py::VARIANTS,
+e.g. autoinit: every automatic variable starts from a bit pattern).  On a mismatch the cells are printed, the case is saved (soak_case_<seed>_<n>.npz) and the same inputs are run
 again through a fresh batch (transient or repeatable?).
 """
 import argparse
@@ -145,7 +144,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--variant", default="")
+    ap.add_argument("--variant", default="", help="a diagnostic build of the library (exomedepth_amd/_build.py::VARIANTS), e.g. autoinit")
     ap.add_argument("--target-cells", type=float, default=None)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
