@@ -161,6 +161,10 @@ SYMBOLS = [
     ("ed_memcpy_d2h", C.c_int, [_vp, _vp, C.c_size_t]),
     ("ed_synchronize", C.c_int, [_vp]),
     ("ed_eval_sf", C.c_int, [C.c_int, _i64, _vp, _vp, _vp]),
+    ("ed_correct_counts_pca", C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _i32, _vp, _vp]),
+    ("ed_pca_gram", C.c_int, [_vp, _i64, _i64, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    ("ed_pca_last_info", C.c_int, [_vp]),
+    ("ed_pca_last_basis", C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i32)]),
 ]
 
 

@@ -1205,7 +1205,7 @@ def cohort_select_reference_sets(counts, bin_length=None, n_bins_reduced=0, max_
     E, S = int(counts.shape[0]), int(counts.shape[1])
     t0, t1 = (0, S) if test_range is None else (int(test_range[0]), int(test_range[1]))
     Sr = t1 - t0
-    if not hasattr(counts, "data_ptr"):
+    if not _is_device(counts):             # (a DeviceArray -- correct_counts_using_PCA's result, say -- is used in place, like a torch CUDA tensor)
         counts = _as_r_integer(np.asarray(counts))
     pc = _device_pointer(counts, np.int32, keep)
     K = int(min(max_refs if max_refs > 0 else 32, S - 1))
@@ -1240,6 +1240,114 @@ def cohort_select_reference_sets(counts, bin_length=None, n_bins_reduced=0, max_
     if corr is not None:
         out["correlations"] = corr
     return out
+
+
+def _pca_inputs(count_data, mask_exons, sample_div):
+    """the input checks of R/PCA_for_read_count.R:43, :60-61 (their messages) shared by the two PCA entries; nothing touches the device yet"""
+    shape = getattr(count_data, "shape", None)
+    if shape is None or len(shape) != 2:
+        raise ValueError("The input to the PCA correction must be a matrix")
+    E, S = int(shape[0]), int(shape[1])
+    if not _is_device(count_data):
+        count_data = _as_r_integer(np.asarray(count_data))
+    mask = None
+    if mask_exons is not None:
+        m = np.asarray(mask_exons)
+        if m.dtype != np.bool_:
+            raise ValueError("The mask exons argument must be a logical vector")
+        if m.ndim != 1 or m.size != E:
+            raise ValueError("The length of the mask exons argument does not match the number of exons")
+        mask = np.ascontiguousarray(m, dtype=np.uint8)
+    div = None
+    if sample_div is not None:
+        div = _f64(sample_div)
+        if div.shape != (S,):
+            raise ValueError("sample_div must hold one value per sample (%d), got shape %s" % (S, div.shape))
+    return E, S, count_data, mask, div
+
+
+def correct_counts_using_PCA(count_data, nPCs=3, mask_exons=None, *, sample_div=None, exon_mul=None, sample_mul=None, sd_min=2.0,
+                             tol=1e-12, max_iter=500, out=None, stream=None):
+    """reference R/PCA_for_read_count.R:41-78: the count matrix with its first nPCs principal components removed, for the whole cohort, on the device.
+
+    count_data: (E, S) host array or torch CUDA int32 tensor, exons by samples.  mask_exons: boolean (E,), exons kept out of the PCA (they are
+    still corrected).  Returns a DeviceArray (E, S) int32 -- or `out`, the caller's own (E, S) int32 device array -- that
+    cohort_select_reference_sets and Cohort.submit take as it is.
+
+    As the reference computes it: the depth normalisation divides sample (column) i by max(1, rowSums(count_data)[i] / 1000) -- the per-EXON
+    vector indexed by the SAMPLE number (:50-51), so it needs S <= E -- and the result is scaled back by rowSums[e] / 1000 per exon (:75).
+    That is what the reference's users get, and the default here.  sample_div (S,), exon_mul (E,), sample_mul (S,) replace those vectors:
+    out = rint(max(0, exon_mul[e] * sample_mul[s] * (residual + centre[e]))); e.g. sample_div = sample_mul = max(1, colSums / 1000),
+    exon_mul = 1 is a per-sample depth normalisation.  sd_min: the reference's 2 (:56).
+    tol, max_iter: the eigenvectors come from a subspace iteration stopped at |G u - theta u| <= tol * theta_1; a call that does not get
+    there raises EdError (never an answer from an unconverged subspace).  pca_last_info() describes the last call.
+    stream: as cohort_select_reference_sets."""
+    keep = []
+    E, S, count_data, mask, div = _pca_inputs(count_data, mask_exons, sample_div)
+    nPCs = int(nPCs)
+    em = sm = None
+    if exon_mul is not None:
+        em = _f64(exon_mul)
+        if em.shape != (E,):
+            raise ValueError("exon_mul must hold one value per exon (%d), got shape %s" % (E, em.shape))
+    if sample_mul is not None:
+        sm = _f64(sample_mul)
+        if sm.shape != (S,):
+            raise ValueError("sample_mul must hold one value per sample (%d), got shape %s" % (S, sm.shape))
+    if out is not None:
+        if tuple(out.shape) != (E, S):
+            raise ValueError("out must have the shape of count_data %s, got %s" % ((E, S), tuple(out.shape)))
+        if not _is_device(out):
+            raise ValueError("out must be a device array (a torch CUDA int32 tensor or a DeviceArray)")
+    pc = _device_pointer(count_data, np.int32, keep)
+    if out is not None:
+        res, po = out, _device_pointer(out, np.int32, keep)
+    else:
+        res = DeviceArray(nbytes=E * S * 4)
+        res.host_dtype, res.shape = np.dtype(np.int32), (E, S)
+        po = res.ptr
+    check(lib().ed_correct_counts_pca(pc, E, S, nPCs, _ptr(mask) if mask is not None else None, _ptr(div) if div is not None else None,
+                                      _ptr(em) if em is not None else None, _ptr(sm) if sm is not None else None, float(sd_min), float(tol),
+                                      int(max_iter), po, C.c_void_p(stream or 0)))
+    return res
+
+
+def pca_gram(count_data, mask_exons=None, *, sample_div=None, sd_min=2.0, stream=None):
+    """The first two stages of correct_counts_using_PCA alone (ed_pca_gram): dict(G (S, S) -- the Gram matrix of the centred, normalised
+    counts over the selected exons, whose eigenvalues are the spectrum to look at before choosing nPCs --, centre (E,), div (S,),
+    selected (E,) bool, n_selected)."""
+    keep = []
+    E, S, count_data, mask, div = _pca_inputs(count_data, mask_exons, sample_div)
+    pc = _device_pointer(count_data, np.int32, keep)
+    G = np.zeros((S, S))
+    centre = np.zeros(E)
+    dv = np.zeros(S)
+    sel = np.zeros(E, dtype=np.uint8)
+    n = C.c_int64(0)
+    check(lib().ed_pca_gram(pc, E, S, _ptr(mask) if mask is not None else None, _ptr(div) if div is not None else None, float(sd_min),
+                            _ptr(G), _ptr(centre), _ptr(dv), _ptr(sel), C.byref(n), C.c_void_p(stream or 0)))
+    return {"G": G, "centre": centre, "div": dv, "selected": sel.astype(bool), "n_selected": int(n.value)}
+
+
+PCA_INFO_N, PCA_INFO_THETA = 96, 16
+
+
+def pca_last_info():
+    """ed_pca_last_info: the last correct_counts_using_PCA of the process that reached its iteration -- dict(converged, iterations, residual (over theta_1), n_selected,
+    block, nPCs, ms (dict: rowstats, gram, eigen, residual, total; device events), gram_slices, rows_per_slice, gap (theta_k / theta_k+1),
+    theta (theta_1 .. theta_{k+1}), U (S, nPCs) the eigenvectors)."""
+    out = (C.c_double * PCA_INFO_N)()
+    check(lib().ed_pca_last_info(out))
+    k = int(out[4])
+    S, kk = C.c_int64(0), C.c_int32(0)
+    check(lib().ed_pca_last_basis(None, 0, C.byref(S), C.byref(kk)))
+    U = np.zeros((int(S.value), int(kk.value)))
+    if U.size:
+        check(lib().ed_pca_last_basis(_ptr(U), U.size, None, None))
+    return {"converged": bool(out[13]), "iterations": int(out[0]), "residual": float(out[1]), "n_selected": int(out[2]), "block": int(out[3]), "nPCs": k,
+            "ms": {"rowstats": float(out[5]), "gram": float(out[6]), "eigen": float(out[7]), "residual": float(out[8]), "total": float(out[9])},
+            "gram_slices": int(out[10]), "rows_per_slice": int(out[11]), "gap": float(out[12]),
+            "theta": np.array([out[PCA_INFO_THETA + i] for i in range(k + 1)]), "U": U}
 
 
 def get_power_betabinom(size, my_phi, my_p, my_alt_p, theory=False, frequentist=False, limit=False):

@@ -18,6 +18,7 @@
 //   edrefset.inc      select.reference.set (R/optimize_reference_set.R:53-148)
 //   edbins.inc        phi.bins > 1 (R/class_definition.R:120-147)
 //   edcov.inc         covariates in the mean model (data + formula, R/class_definition.R:86-118)
+//   edpca.inc         correct.counts.using.PCA for a cohort (R/PCA_for_read_count.R:41-78)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off  (contraction off is part of the contract:
 // the arithmetic must match the CPU checker bit for bit).
 #include <hip/hip_runtime.h>
@@ -3510,3 +3511,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edcohort.inc"
 #include "edmulti.inc"
 #include "edrefcohort.inc"
+#include "edpca.inc"

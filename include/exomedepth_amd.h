@@ -675,6 +675,45 @@ int ed_select_reference_set_host(const int32_t* test, const int32_t* refs_colmaj
                                  const double* bin_length, int64_t n_bins_reduced, ed_refset_row* rows, int32_t* n_chosen,
                                  int64_t* n_selected_bins);
 
+/* =====================================================================================
+ * Cohort-wide PCA correction of the count matrix -- correct.counts.using.PCA (reference R/PCA_for_read_count.R:41-78)
+ * ===================================================================================== */
+
+/* d_counts int32 [n_exons][n_samples] on the device (the layout ed_cohort_select_reference_sets takes); d_out the same shape, on the device.
+ * With rs[e] = rowSums(counts)[e] / 1000 (:50):
+ *   N[e][s] = counts[e][s] / div[s]                      div = sample_div, or (NULL) the reference's max(1, rs[s]) -- the per-exon vector indexed
+ *                                                        by the sample number (:51), which needs n_samples <= n_exons
+ *   centre[e] = mean_s N[e][s]; selected[e] = sd_s(N[e][.]) > sd_min (n - 1 denominator; the reference's 2) and not mask_exons[e]  (:55-56, :63)
+ *   U = the top n_pcs eigenvectors of G = sum over the selected exons of z z^T, z = N[e][.] - centre[e]   (prcomp, :63-68)
+ *   d_out[e][s] = rint(max(0, exon_mul[e] * sample_mul[s] * (z[s] - (U U^T z)[s] + centre[e]))) for EVERY exon  (:70-75)
+ *                                                        exon_mul NULL = rs[e] (the reference's), sample_mul NULL = 1
+ * mask_exons uint8[n_exons], sample_div / sample_mul double[n_samples], exon_mul double[n_exons]: HOST arrays, each may be NULL.
+ * The eigenvectors come from a block subspace iteration (block min(n_samples, max(2 n_pcs, n_pcs + 8))) with Rayleigh-Ritz, stopped when
+ * max_{i <= n_pcs} |G u_i - theta_i u_i| <= tol * theta_1.  Not converged within max_iter iterations: ED_ERR_STATE, ed_last_error() names the
+ * iterations, the residual reached and theta_k / theta_k+1 -- never an answer from an unconverged subspace.
+ * ED_ERR_INVALID (with a message): n_pcs < 1, n_pcs > 64, n_pcs >= min(n_samples, selected exons), n_samples > n_exons with sample_div NULL,
+ * n_samples > 32768, no exon selected, a sample_div that is not finite and positive.
+ * The entry returns when its work is complete; its kernels and copies are issued on `stream`. */
+int ed_correct_counts_pca(const int32_t* d_counts, int64_t n_exons, int64_t n_samples, int32_t n_pcs, const uint8_t* mask_exons,
+                          const double* sample_div, const double* exon_mul, const double* sample_mul, double sd_min, double tol,
+                          int32_t max_iter, int32_t* d_out, void* stream);
+
+/* The first two stages alone (row statistics, Gram matrix), to HOST arrays: G_out [n_samples][n_samples]; optional centre_out [n_exons],
+ * div_out [n_samples], selected_out uint8[n_exons], *n_selected.  G is symmetric and the same bits on every run (its partial sums over
+ * slices of the selected exons are added in a fixed order).  What a caller looks at (the spectrum of G) before choosing n_pcs. */
+int ed_pca_gram(const int32_t* d_counts, int64_t n_exons, int64_t n_samples, const uint8_t* mask_exons, const double* sample_div, double sd_min,
+                double* G_out, double* centre_out, double* div_out, uint8_t* selected_out, int64_t* n_selected, void* stream);
+
+/* The last ed_correct_counts_pca of the process that reached its iteration: out[0] iterations, [1] residual / theta_1, [2] selected exons, [3] block size b,
+ * [4] n_pcs, [5..8] milliseconds of the stages (row statistics, Gram, eigenvectors, residual pass; device events), [9] their total,
+ * [10] slices of the Gram kernel, [11] selected rows per slice, [12] theta_k / theta_k+1, [13] 1 = converged (0: the call
+ * returned ED_ERR_STATE; [8], [9] are then zero and [7] is the time spent iterating), [ED_PCA_INFO_THETA + i] theta_1 .. theta_{n_pcs + 1}. */
+#define ED_PCA_INFO_N 96
+#define ED_PCA_INFO_THETA 16
+int ed_pca_last_info(double out[ED_PCA_INFO_N]);
+/* ... and its eigenvectors U [n_samples][n_pcs] (cap = room in U_out, in values; U_out NULL: the dimensions only) */
+int ed_pca_last_basis(double* U_out, int64_t cap, int64_t* n_samples, int32_t* n_pcs);
+
 /* ---- utilities ---- */
 /* device memory through the library, for callers without a HIP binding (tests, R shim) */
 int ed_malloc(void** dptr, size_t bytes);
