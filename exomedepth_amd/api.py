@@ -1278,7 +1278,10 @@ def correct_counts_using_PCA(count_data, nPCs=3, mask_exons=None, *, sample_div=
     vector indexed by the SAMPLE number (:50-51), so it needs S <= E -- and the result is scaled back by rowSums[e] / 1000 per exon (:75).
     That is what the reference's users get, and the default here.  sample_div (S,), exon_mul (E,), sample_mul (S,) replace those vectors:
     out = rint(max(0, exon_mul[e] * sample_mul[s] * (residual + centre[e]))); e.g. sample_div = sample_mul = max(1, colSums / 1000),
-    exon_mul = 1 is a per-sample depth normalisation.  sd_min: the reference's 2 (:56).
+    exon_mul = 1 is a per-sample depth normalisation.  Saturation: with v the product before rounding, out = rint(min(2147483647, max(0, v))),
+    rint half-even; a negative v and a NaN v (an infinite multiplier times a zero one) give 0 -- R's pmax(0, .) keeps the NaN, an int32 cannot --
+    and a v above the int32 range, +inf included, gives exactly 2147483647.  The multipliers are not checked: zero, negative and infinite values
+    follow this rule.  sd_min: the reference's 2 (:56).
     tol, max_iter: the eigenvectors come from a subspace iteration stopped at |G u - theta u| <= tol * theta_1; a call that does not get
     there raises EdError (never an answer from an unconverged subspace).  pca_last_info() describes the last call.
     stream: as cohort_select_reference_sets."""

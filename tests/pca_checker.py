@@ -18,6 +18,19 @@ def make_counts(E, S, seed, groups=True):
     return rng.poisson(lam[:, None] * sf[None, :] * np.exp(gn[:, grp] + own)).astype(np.int32)
 
 
+def make_planted(E, S, k, seed, amp=0.6):
+    """make_counts with the six batch groups replaced by k planted factors (a spectrum with k components above the noise, whatever k):
+    rate x exp(F L + own), F ~ N(0, amp / sqrt(k)) (E x k), L ~ N(0, 1) (k x S).  Draw order: lam, the empty mask, sf, F, L, own, poisson."""
+    rng = np.random.default_rng(seed)
+    lam = rng.lognormal(np.log(90), 0.9, E)
+    lam[rng.random(E) < 0.08] *= 0.01
+    sf = rng.lognormal(0, 0.25, S)
+    F = rng.normal(0, amp / np.sqrt(k), (E, k))
+    L = rng.normal(0, 1, (k, S))
+    own = rng.normal(0, 0.05, (E, S))
+    return rng.poisson(lam[:, None] * sf[None, :] * np.exp(F @ L + own)).astype(np.int32)
+
+
 def correct_counts_using_PCA(count_data, nPCs=3, mask_exons=None, sample_div=None, exon_mul=None, sample_mul=None, sd_min=2.0):
     C = np.asarray(count_data, dtype=np.float64)
     nexons, nsamples = C.shape                                      # :44-45
