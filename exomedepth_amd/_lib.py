@@ -165,6 +165,11 @@ SYMBOLS = [
     ("ed_pca_gram", C.c_int, [_vp, _i64, _i64, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
     ("ed_pca_last_info", C.c_int, [_vp]),
     ("ed_pca_last_basis", C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i32)]),
+    ("ed_annot_create", C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    ("ed_annot_destroy", None, [_vp]),
+    ("ed_annot_n", _i64, [_vp]),
+    ("ed_annot_overlaps", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
+    ("ed_annot_geometry", C.c_int, [C.POINTER(_i32)]),
 ]
 
 

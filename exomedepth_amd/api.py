@@ -1100,6 +1100,24 @@ class ExomeDepth:
         return self
 
 
+    def AnnotateExtra(self, reference_annotation, min_overlap=0.5, column_name=None):
+        """reference R/annotate_extra.R:41-73: adds `column_name` to every row of CNV_calls -- the `names` of the annotation's intervals the
+        call overlaps by more than min_overlap x (end - start), joined with ",", or None where R leaves NA (no such interval).
+        reference_annotation: an Annotation built with names (what stands for the GRanges and its `names` metadata column).  The names
+        of one call come in genomic order of the annotation's intervals (Annotation.overlaps)."""
+        if column_name is None:
+            raise TypeError('argument "column_name" is missing, with no default')     # as the R generic: no default
+        if not isinstance(reference_annotation, Annotation) or reference_annotation.names is None:
+            raise ValueError("reference_annotation must be an Annotation with names")
+        calls = self.CNV_calls or []
+        if calls:
+            _, offsets, hits = reference_annotation.overlaps([c["chromosome"] for c in calls], [c["start"] for c in calls],
+                                                             [c["end"] for c in calls], min_overlap=min_overlap)
+            for c, v in zip(calls, _join_hit_names(reference_annotation.names, offsets, hits)):
+                c[column_name] = v
+        return self
+
+
 def somatic_CNV_call(normal, tumor, prop_tumor=1.0, chromosome=None, start=None, end=None, names=None):
     """reference R/class_definition.R:442-461: one matched tumour / normal pair -- new('ExomeDepth', test = tumor, reference = normal,
     prop.tumor = prop_tumor) (the fit ignores prop_tumor; the likelihood sees it) followed by CallCNVs(transition.probability = 1e-4)
@@ -1114,6 +1132,163 @@ def somatic_CNV_call(normal, tumor, prop_tumor=1.0, chromosome=None, start=None,
     x = ExomeDepth(test=tumor, reference=normal, prop_tumor=prop_tumor, formula="cbind(test, reference) ~ 1")
     sys.stderr.write("Now calling the CNVs\n")
     return x.CallCNVs(chromosome, start, end, names, transition_probability=1e-4)
+
+
+# ---------------------------------------------------------------------------------------------
+# annotation overlap (reference R/annotate_extra.R:41-73) and the cohort's self-join
+# ---------------------------------------------------------------------------------------------
+def _join_hit_names(names, offsets, hits):
+    """paste(names[hits of call q], collapse = ",") per call, None where the call has no hit (R/annotate_extra.R:67-71)"""
+    return [",".join(str(names[int(h)]) for h in hits[int(offsets[q]):int(offsets[q + 1])]) if offsets[q + 1] > offsets[q] else None
+            for q in range(len(offsets) - 1)]
+
+
+def annot_geometry():
+    """{wide_threshold, queries_per_workgroup, wave_pass, scan_block} of the join kernels (ed_annot_geometry): for tests placing shapes on the edges"""
+    out = (C.c_int32 * 4)()
+    check(lib().ed_annot_geometry(out))
+    return dict(zip(("wide_threshold", "queries_per_workgroup", "wave_pass", "scan_block"), (int(v) for v in out)))
+
+
+def _coords(start, end):
+    """int32 coordinates; a value that int32 cannot hold is refused here instead of wrapping silently"""
+    out = []
+    for a in (np.asarray(start), np.asarray(end)):
+        if a.size:
+            if a.dtype.kind not in "iu" and not (a.dtype.kind == "f" and np.all(a == np.trunc(a))):
+                raise ValueError("interval coordinates must be integers")
+            if a.min() < -2**31 or a.max() > 2**31 - 1:
+                raise ValueError("interval coordinates must fit int32")
+        out.append(_i32(a).ravel())
+    return out
+
+
+class Annotation:
+    """An annotation track on the device (ed_annot): intervals `chromosome`, `start`, `end` (closed, 0 <= start <= end), optionally with
+    `names` (what AnnotateExtra pastes), a `group` and a `kind` per interval (int32; the two optional filters of overlaps()).
+    Chromosome names are mapped to ids here; "chr1" and "1" are DIFFERENT names, as in GenomicRanges.
+    Every interval must have 0 <= start <= end: a zero-width row (end == start - 1, which IRanges accepts as an empty range and some exon
+    designs carry) is refused with the rest -- it can overlap nothing, so the caller leaves such rows out (and keeps its own indices as names)."""
+
+    def __init__(self, chromosome, start, end, names=None, group=None, kind=None, device=0):
+        chrom = np.asarray([str(c) for c in chromosome], dtype=object)
+        self.start, self.end = _coords(start, end)
+        if not (chrom.size == self.start.size == self.end.size):
+            raise ValueError("chromosome, start and end must have the same length")
+        self.n = int(self.start.size)
+        levels, codes = np.unique(chrom.astype(str), return_inverse=True) if self.n else (np.zeros(0, dtype=str), np.zeros(0, np.int64))
+        self.levels = [str(x) for x in levels]
+        self._code_of = {c: i for i, c in enumerate(self.levels)}
+        self.chrom = _i32(codes)
+        self.names = None if names is None else np.asarray(names, dtype=object)
+        if self.names is not None and self.names.size != self.n:
+            raise ValueError("names must have one entry per interval")
+        self.group = None if group is None else _i32(group).ravel()
+        self.kind = None if kind is None else _i32(kind).ravel()
+        for a in (self.group, self.kind):
+            if a is not None and a.size != self.n:
+                raise ValueError("group / kind must have one entry per interval")
+        self.handle = C.c_void_p()
+        check(lib().ed_annot_create(C.byref(self.handle), int(device), self.n, len(self.levels), _ptr(self.chrom), _ptr(self.start),
+                                    _ptr(self.end), None if self.group is None else _ptr(self.group),
+                                    None if self.kind is None else _ptr(self.kind)))
+
+    def close(self):
+        if self.handle:
+            lib().ed_annot_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def chromosome_ids(self, chromosome):
+        """ids of query chromosome names; a name the track does not have is -1 (no hits)"""
+        chrom = np.asarray([str(c) for c in chromosome], dtype=str)
+        if chrom.size == 0:
+            return np.zeros(0, np.int32)
+        u, inv = np.unique(chrom, return_inverse=True)
+        return _i32(np.asarray([self._code_of.get(str(x), -1) for x in u], dtype=np.int32)[inv])
+
+    def overlaps(self, chromosome, start, end, min_overlap=0.5, group=None, kind=None, want_hits=True):
+        """The intervals of the track every query interval hits (include/exomedepth_amd.h, "Annotation overlap": the overlap of
+        R/annotate_extra.R:63-65, `ov > min_overlap * (end - start)` with ov = min(ends) - max(starts), no + 1).
+        group / kind (int32 per query): drop pairs of equal group / keep only pairs of equal kind; the track must have been given the array.
+        Returns (counts int64 [n_q], offsets int64 [n_q + 1], hits int32 [offsets[-1]]): query q hits the track's intervals
+        hits[offsets[q]:offsets[q + 1]] (indices into the arrays the track was made from), ascending by (start, index).  want_hits=False:
+        hits is None (count only).  A chromosome name the track does not have gives no hits."""
+        if not self.handle:
+            raise EdError("Annotation is closed")
+        qs, qe = _coords(start, end)
+        qc = self.chromosome_ids(chromosome)
+        n_q = int(qs.size)
+        if not (qc.size == n_q == qe.size):
+            raise ValueError("chromosome, start and end must have the same length")
+        qg = None if group is None else _i32(group).ravel()
+        qk = None if kind is None else _i32(kind).ravel()
+        for a in (qg, qk):
+            if a is not None and a.size != n_q:
+                raise ValueError("group / kind must have one entry per query")
+        counts = np.zeros(n_q, np.int64)
+        offsets = np.zeros(n_q + 1, np.int64)
+        total = C.c_int64(0)
+        args = (self.handle, n_q, _ptr(qc), _ptr(qs), _ptr(qe), None if qg is None else _ptr(qg), None if qk is None else _ptr(qk),
+                float(min_overlap), _ptr(counts), _ptr(offsets))
+        if not want_hits:
+            check(lib().ed_annot_overlaps(*args, None, 0, C.byref(total)))
+            return counts, offsets, None
+        # one call when the guess holds the hits; the library reports the total either way and writes nothing when they do not fit
+        hits = np.empty(max(1024, 4 * n_q), np.int32)
+        rc = lib().ed_annot_overlaps(*args, _ptr(hits), hits.size, C.byref(total))
+        if rc != _lib.ED_OK and total.value > hits.size:
+            hits = np.empty(total.value, np.int32)
+            rc = lib().ed_annot_overlaps(*args, _ptr(hits), hits.size, C.byref(total))
+        check(rc)
+        return counts, offsets, hits if hits.size == total.value else hits[:total.value].copy()
+
+
+def _call_intervals(calls, chromosome_names, exon_start, exon_end):
+    """a structured ed_call array as genomic intervals, as CallCNVs makes them: start[start_exon], end[end_exon], the plan's chromosome level"""
+    calls = np.asarray(calls)
+    names = np.asarray([str(c) for c in chromosome_names], dtype=object)
+    es, ee = np.asarray(exon_start), np.asarray(exon_end)
+    return names[calls["chrom"]], es[calls["start_exon"]], ee[calls["end_exon"]]
+
+
+def annotate_calls(calls, chromosome_names, exon_start, exon_end, annotation, min_overlap=0.5):
+    """AnnotateExtra for a cohort's call table: `calls` is the structured ed_call array of Batch.calls(), Cohort.results(...) or
+    MultiDevice.run_host(...), chromosome_names the plan's chromosome levels (calls["chrom"] indexes them), exon_start / exon_end the
+    plan's exon coordinates.  Returns (counts, offsets, hits) of Annotation.overlaps for the calls in table order."""
+    chrom, start, end = _call_intervals(calls, chromosome_names, exon_start, exon_end)
+    return annotation.overlaps(chrom, start, end, min_overlap=min_overlap)
+
+
+def cohort_call_recurrence(calls, chromosome_names, exon_start, exon_end, min_overlap=0.5, same_type=True, carriers=False, device=0):
+    """The call table joined against itself under AnnotateExtra's rule: per call, the number of calls of OTHER samples that overlap it by more
+    than min_overlap x its own length (the rule is asymmetric: a short call inside a long one counts the long one, not the reverse, for
+    min_overlap near 1) -- of the same type only when same_type is set.  The group is the sample, so a call never counts itself or its
+    sample-mates.  carriers=True returns (n_calls, n_carriers) with n_carriers the number of DISTINCT other samples among those calls; the join
+    (windows, tests, filters, compaction) runs on the device, the distinct count is made on the host from the CSR result."""
+    calls = np.asarray(calls)
+    chrom, start, end = _call_intervals(calls, chromosome_names, exon_start, exon_end)
+    sample = _i32(calls["sample"])
+    kind = _i32(calls["type"]) if same_type else None
+    track = Annotation(chrom, start, end, group=sample, kind=kind, device=device)
+    try:
+        counts, offsets, hits = track.overlaps(chrom, start, end, min_overlap=min_overlap, group=sample, kind=kind, want_hits=bool(carriers))
+    finally:
+        track.close()
+    if not carriers:
+        return counts
+    n = calls.size
+    if n == 0 or hits.size == 0:
+        return counts, np.zeros(n, np.int64)
+    K = int(sample.max()) + 1
+    pairs = np.unique(np.repeat(np.arange(n, dtype=np.int64), counts) * K + sample[hits])     # distinct (call, other sample)
+    n_carriers = np.bincount(pairs // K, minlength=n).astype(np.int64)
+    return counts, n_carriers
 
 
 REFSET_DTYPE = np.dtype([("ref_index", "<i4"), ("selected", "<i4"), ("correlation", "<f8"), ("expected_BF", "<f8"),

@@ -3512,3 +3512,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edmulti.inc"
 #include "edrefcohort.inc"
 #include "edpca.inc"
+#include "edannot.inc"

@@ -714,6 +714,52 @@ int ed_pca_last_info(double out[ED_PCA_INFO_N]);
 /* ... and its eigenvectors U [n_samples][n_pcs] (cap = room in U_out, in values; U_out NULL: the dimensions only) */
 int ed_pca_last_basis(double* U_out, int64_t cap, int64_t* n_samples, int32_t* n_pcs);
 
+/* =====================================================================================
+ * Annotation overlap: AnnotateExtra (reference R/annotate_extra.R:41-73) and the cohort's self-join -- csrc/edannot.inc
+ * ===================================================================================== */
+
+/* An interval join of a call table (the queries) against an annotation track (the subjects), both closed integer ranges on chromosomes
+ * given as ids 0 .. n_chrom - 1 (names are matched by the caller).  A query [qs, qe] on chromosome c and a subject [ss, se] on c' are a HIT iff
+ *   c == c'
+ *   qs <= se && ss <= qe                               findOverlaps(query, subject), type "any" (:46)
+ *   (double)ov > min_overlap * (double)(qe - qs)       ov = min(se, qe) - max(qs, ss), as :63-65 compute it: NO + 1 on either side
+ * and, when asked for (not in the reference; the cohort's self-join uses both),
+ *   group filter: the query's group differs from the subject's (the group is the sample: a call never hits its own sample's calls)
+ *   kind filter:  the query's kind equals the subject's (deletion / duplication).
+ * The reference's quirks follow from the ov formula and are kept: a query with qs == qe is never annotated (0 > 0 fails at any min_overlap);
+ * a subject that touches the query in one base never counts (ov = 0); at min_overlap = 0 every overlap of two or more bases counts; a subject
+ * covering the whole query gives ov == qe - qs, a hit for min_overlap < 1 and none at 1.  The comparison is one binary64 multiplication and
+ * one compare of exactly represented integers, so the device and a host restatement agree bit for bit.
+ * Order: hits are grouped by query, in the caller's query order; within a query they come in genomic order of the subjects, ascending
+ * (subject start, subject's index in the caller's order).  GenomicRanges documents the order by query only, so the order within a query is
+ * THIS library's definition; it does not depend on which kernel served the query.
+ * Coordinates are int32 with 0 <= start <= end, everywhere: anything else is ED_ERR_INVALID before any device work.
+ *
+ * ed_annot_create sorts the subjects (stably, by start within a chromosome), forms the running maximum of `end` over that order and uploads
+ * both: a query's candidates are then the window between two binary searches, and the track is reused by every later query
+ * set.  group / kind: int32 [n] or NULL; a filter can only be asked of a track that was given the array.  n == 0 is valid.
+ * An object is not for two threads at a time (it owns one stream and the scratch of its last query set); it sets its device on every call. */
+typedef struct ed_annot ed_annot;
+int ed_annot_create(ed_annot** annot, int device, int64_t n, int32_t n_chrom, const int32_t* chrom, const int32_t* start, const int32_t* end,
+                    const int32_t* group /* or NULL */, const int32_t* kind /* or NULL */);
+void ed_annot_destroy(ed_annot* annot);
+int64_t ed_annot_n(const ed_annot* annot);
+/* All arrays are HOST memory.  counts[q] = hits of query q; offsets (optional) their exclusive scan, offsets[n_q] = the total; *n_hits is
+ * ALWAYS the total.  hits == NULL: count only.  Otherwise hits[offsets[q] .. offsets[q + 1]) receives query q's subjects as indices into the
+ * arrays ed_annot_create was given; if the total exceeds cap NOTHING is written to hits and the call returns ED_ERR_INVALID with a message
+ * that names the room needed (counts, offsets and *n_hits are complete): count first, fill second.  A q_chrom outside 0 .. n_chrom - 1 is
+ * a chromosome the track does not have: no hits.  q_group / q_kind NULL = that filter off; non-NULL on a track created without the array,
+ * a min_overlap that is negative or not finite: ED_ERR_INVALID.  n_q == 0 is valid. */
+int ed_annot_overlaps(ed_annot* annot, int64_t n_q, const int32_t* q_chrom, const int32_t* q_start, const int32_t* q_end,
+                      const int32_t* q_group /* or NULL */, const int32_t* q_kind /* or NULL */, double min_overlap,
+                      int64_t* counts /* [n_q] */, int64_t* offsets /* [n_q + 1] or NULL */,
+                      int32_t* hits /* subject indices in the caller's order, [cap], or NULL = count only */,
+                      int64_t cap, int64_t* n_hits);
+/* Launch geometry of the join, for tests that place their shapes on its edges: out = {W, B, P, S}.  A query whose window holds more than W
+ * subjects is served by a wavefront (P = 64 subjects a pass), the others by one lane each, B queries a workgroup; the scan of the counts
+ * gives S values to a workgroup.  No result depends on any of them. */
+int ed_annot_geometry(int32_t out[4]);
+
 /* ---- utilities ---- */
 /* device memory through the library, for callers without a HIP binding (tests, R shim) */
 int ed_malloc(void** dptr, size_t bytes);
