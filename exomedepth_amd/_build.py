@@ -71,6 +71,9 @@ VARIANTS = {# every automatic variable starts from a bit pattern (0xAA...) inste
             # k_fit_hnewton's per-cell path with the short digamma series (irreproducible fits), alone and with pattern-initialised variables
             "hnshort": ["-DED_HN_SHORT_SERIES"], "hnshortinit": ["-DED_HN_SHORT_SERIES", "-ftrivial-auto-var-init=pattern"],
             "hnshortplain": ["-DED_HN_SHORT_SERIES", "-DED_FIT_PLAIN_FMA"], "fitplain": ["-DED_FIT_PLAIN_FMA"],
+            # k_tb_paths also writes the byte-per-exon path in every run, as it did before the path was made on request (edcore.hip, trace-back
+            # block): the other side of tools/ab.sh eagerpath
+            "eagerpath": ["-DED_EAGER_BYTE_PATH"],
             # host code under the sanitizers (device code is left alone: -fno-gpu-sanitize); tools/sanitize.sh
             # (no -shared-libsan: the runtime is whatever tools/sanitize.sh preloads -- gcc's stock libasan / libtsan; ROCm's own
             # ASan runtime intercepts hsa_amd_memory_pool_allocate for DEVICE instrumentation and fails on a plain process)

@@ -1039,6 +1039,7 @@ static int cohort_collect(ed_cohort* c, int64_t ticket, int64_t sample0, int64_t
   if (phi_out) { if (int rc = ed_d2h(phi_out + sample0, sl.d_phi, (size_t)n * 8, b->stream)) return rc; }
   if (expected_out) { if (int rc = ed_d2h(expected_out + sample0, sl.d_exp, (size_t)n * 8, b->stream)) return rc; }
   if (path_out && E > 0) {
+    if (int rc = ensure_path(b)) return rc;
     if (layout == 1) {
       if (!sl.path_cols) HIP_TRY(hipMalloc((void**)&sl.path_cols, (size_t)E * c->slab));
       hipLaunchKernelGGL(k_rows_to_cols<uint8_t>, dim3((unsigned)((E + 63) / 64), (unsigned)((n + 63) / 64)), dim3(256), 0, b->stream, (const uint8_t*)b->d_path, E, n,

@@ -843,8 +843,19 @@ k_viterbi(const double* __restrict__ loglik, const double* __restrict__ lt4, dou
 //   k_tb_chain  one lane per chain: walk the ~m/16 maps from the last word down, recording the state of each
 //               word's last exon (a 3-instruction dependent step per 16 exons)
 //   k_tb_paths  every (sample, word) in parallel: replay the 16 steps from the now known state, write the
-//               packed states, the byte-per-exon path of the interface, and count the calls (a call ends
-//               wherever a run of a non-zero state ends, src/hmm.cpp:109-121; integer atomics: exact)
+//               packed states (ppath) and count the calls (a call ends wherever a run of a non-zero state
+//               ends, src/hmm.cpp:109-121; integer atomics: exact)
+// Nothing in a run reads the byte-per-exon path [E][S] of the interface -- the call table, its statistics and
+// its decoration come from ppath -- so a run does not write it: 16 one-byte stores per thread, S bytes apart,
+// a 64-byte half line per wave instruction.  It is made on request from ppath (k_path_expand through
+// ensure_path, ed_batch::path_valid), as the [E][3][S] likelihood matrix of emit mode 2 is.  k_tb_paths<true>
+// is the form that writes it in every run: the diagnostic build "eagerpath" (ED_EAGER_BYTE_PATH) only, the
+// other side of an A/B of this choice.
+#ifdef ED_EAGER_BYTE_PATH
+constexpr bool kEagerPath = true;
+#else
+constexpr bool kEagerPath = false;
+#endif
 __device__ __forceinline__ uint32_t tb_pick(const uint4& w, int st) { return st == 0 ? w.x : (st == 1 ? w.y : w.z); }
 
 __global__ void __launch_bounds__(256)
@@ -920,6 +931,7 @@ k_tb_chain(const int32_t* __restrict__ chrom_off, const int64_t* __restrict__ wo
   }
 }
 
+template <bool kBytes>
 __global__ void __launch_bounds__(256)
 k_tb_paths(const uint32_t* __restrict__ bpq, const int32_t* __restrict__ chrom_off, const int64_t* __restrict__ word_off,
            int64_t S, int32_t C, const int32_t* __restrict__ job_off, const int32_t* __restrict__ job_chrom, int job_base,
@@ -939,12 +951,12 @@ k_tb_paths(const uint32_t* __restrict__ bpq, const int32_t* __restrict__ chrom_o
     int st = (int)((ent[((word_off[c] >> 4) + c + (w >> 4)) * S + s] >> (2 * (int)(w & 15))) & 3u);   // state of exon 16w + n - 1
     int count = ((w + 1) * kVitTile >= m && st != 0) ? 1 : 0;  // the chromosome's last exon against the dummy end state 0
     uint32_t pw = 0;
-    uint8_t* __restrict__ o = path + (lo + w * kVitTile) * S + s;
+    uint8_t* __restrict__ o = kBytes ? path + (lo + w * kVitTile) * S + s : nullptr;
 #pragma unroll
     for (int k = kVitTile - 1; k >= 0; --k) {
       if (k < n) {
         pw |= (uint32_t)st << (2 * k);
-        o[(int64_t)k * S] = (uint8_t)st;
+        if constexpr (kBytes) o[(int64_t)k * S] = (uint8_t)st;
         const int prev = (int)((tb_pick(bw, st) >> (2 * k)) & 3u);   // state of exon 16w + k - 1
         if ((k > 0 || w > 0) && prev != st && prev != 0) ++count;
         st = prev;
@@ -1762,6 +1774,7 @@ struct ed_batch {
   const double* last_cov_beta = nullptr;
   int last_cov_K = -1;
   bool ran = false;
+  bool path_valid = true;    // d_path holds the byte-per-exon path of the last run; a run clears it, ensure_path makes the path from ppath
   bool fused = false;        // run emissions + Viterbi as ONE kernel (edfused.inc) instead of two overlapped ones
   bool keep_loglik = true;   // fused mode only: also write the [E][3][S] likelihood matrix (the S4 `likelihood` slot)
   int fit_hist = 1;          // ed_batch_fit: 1 = iterate on count histograms (one pass over the counts), geometry picked from
@@ -2532,6 +2545,24 @@ static int ensure_loglik_rows(ed_batch* b)
   return ED_OK;
 }
 
+// the byte-per-exon path [E][S] of the interface, made from the packed states when somebody asks for it: on the stream the run's
+// results become available on, behind the run.  With an asynchronous tail done_ev is moved behind it, so that the batch's next run
+// (which rewrites ppath) waits for it as it does for the tail.
+static int ensure_path(ed_batch* b)
+{
+  if (b->path_valid) return ED_OK;
+  HIP_TRY(hipSetDevice(b->plan->device));
+  const ed_plan* p = b->plan;
+  if (p->C > 0 && p->E > 0 && p->max_words > 0) {
+    hipLaunchKernelGGL(k_path_expand, dim3((unsigned)((b->S + 63) / 64), (unsigned)((p->max_words + 3) / 4), (unsigned)p->C), dim3(256),
+                       0, b->stream, b->d_ppath, p->d_chrom_off, p->d_tile_off, b->S, b->d_path);
+    HIP_TRY(hipGetLastError());
+    if (b->last_run_async && b->done_ev) HIP_TRY(hipEventRecord(b->done_ev, b->stream));
+  }
+  b->path_valid = true;
+  return ED_OK;
+}
+
 // after k_sample_consts: table lengths from a subsampled pass over the counts, then the entries
 static int tab_build(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, hipStream_t st)
 {
@@ -2597,6 +2628,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
   const bool tabm = plain && b->emit_mode >= 1 && !b->fused;   // emissions from log-gamma difference tables (edtab.inc)
   const bool tabsm = tabm && b->emit_mode == 2;                // ... sample-major form: tables in LDS, [S][3][Epad] likelihood matrix
   b->rows_valid = !tabsm;
+  b->path_valid = kEagerPath && !b->fused;   // the byte path is made when it is asked for (ensure_path)
   const bool cl1 = b->counts_layout == 1;                       // counts handed over sample-major [S][E]
   if (cl1 && !tabsm) return ed_fail(ED_ERR_STATE, "ed_batch_run: sample-major counts (ed_batch_set_counts_layout(batch, 1)) are served by emit mode 2 only");
   if (b->counts_bits == 16 && !(cl1 && tabsm)) return ed_fail(ED_ERR_STATE, "ed_batch_run: 16-bit counts (ed_batch_set_counts_bits(batch, 16)) are served by counts_layout 1 + emit mode 2 only");
@@ -2801,7 +2833,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
                          b->d_job_chrom, j0, b->d_maps);
       hipLaunchKernelGGL(k_tb_chain, dim3((unsigned)((S + kWave - 1) / kWave), (unsigned)(j1 - j0)), dim3(kWave), 0, side,
                          p->d_chrom_off, p->d_tile_off, S, b->d_job_off, b->d_job_chrom, j0, b->d_last, b->d_maps, b->d_ent);
-      hipLaunchKernelGGL(k_tb_paths, gw, dim3(256), 0, side, b->d_bp, p->d_chrom_off, p->d_tile_off, S, C, b->d_job_off,
+      hipLaunchKernelGGL(k_tb_paths<kEagerPath>, gw, dim3(256), 0, side, b->d_bp, p->d_chrom_off, p->d_tile_off, S, C, b->d_job_off,
                          b->d_job_chrom, j0, b->d_ent, b->d_ppath, b->d_path, b->d_counts);
       HIP_TRY(hipEventRecord(b->join_ev[g], side));
     }
@@ -2812,9 +2844,6 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
     }
     for (size_t g = 0; g + 1 < b->group_off.size() && cells > 0; ++g) HIP_TRY(hipStreamWaitEvent(tail, b->join_ev[g], 0));
   }
-  if (b->fused && C > 0 && cells > 0 && p->max_words > 0)   // (the two-kernel path writes the byte path in k_tb_paths)
-    hipLaunchKernelGGL(k_path_expand, dim3((unsigned)((S + 63) / 64), (unsigned)((p->max_words + 3) / 4), (unsigned)C), dim3(256),
-                       0, st, b->d_ppath, p->d_chrom_off, p->d_tile_off, S, b->d_path);
   if (b->timing) HIP_TRY(hipEventRecord(b->ev[3], tail));
   hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, tail, b->d_counts, (C > 0 && cells > 0) ? S * C : 0,
                      b->d_offsets, b->d_total);
@@ -3216,7 +3245,17 @@ try {
   return ED_OK;
 }
 ED_CATCH("ed_batch_keep_loglik")
-ED_EXPORT const uint8_t* ed_batch_path(const ed_batch* b) { return b ? b->d_path : nullptr; }
+// (the first call after a run makes the path from the packed states and waits for it: the pointer's reader is on a stream of its own)
+ED_EXPORT const uint8_t* ed_batch_path(const ed_batch* b_)
+{
+  ed_batch* b = const_cast<ed_batch*>(b_);
+  if (!b) return nullptr;
+  if (!b->path_valid) {
+    if (ensure_path(b) != ED_OK) return nullptr;
+    if (hipStreamSynchronize(b->stream) != hipSuccess) { (void)ed_fail(ED_ERR_HIP, "ed_batch_path: the run or the path's expansion failed"); return nullptr; }
+  }
+  return b->d_path;
+}
 ED_EXPORT const ed_call* ed_batch_calls(const ed_batch* b) { return b ? b->d_calls : nullptr; }
 
 static int batch_ready(ed_batch* b)
@@ -3307,6 +3346,7 @@ ED_EXPORT int ed_batch_copy_path(ed_batch* b, uint8_t* host_path)
 try {
   if (int rc = batch_ready(b)) return rc;
   if (!host_path) return ed_fail(ED_ERR_INVALID, "NULL output");
+  if (int rc = ensure_path(b)) return rc;
   if (int rc = ed_d2h(host_path, b->d_path, (size_t)b->plan->E * b->S, b->stream)) return rc;
   return ED_OK;
 }

@@ -262,7 +262,9 @@ const double* ed_batch_loglik(const ed_batch* batch);  /* [n_exons][3][n_samples
                                                          * the first call after a run then ENQUEUES the conversion on the run's stream (and allocates
                                                          * the [n_exons][3][n_samples] form once) -- not for two threads at a time; NULL + ed_last_error()
                                                          * on failure */
-const uint8_t* ed_batch_path(const ed_batch* batch);   /* [n_exons][n_samples]    */
+const uint8_t* ed_batch_path(const ed_batch* batch);   /* [n_exons][n_samples]; a run keeps the states packed (16 exons per word): the first call after a
+                                                         * run makes this form on the run's stream and WAITS for it (so does ed_batch_copy_path; later
+                                                         * calls launch nothing) -- not for two threads at a time; NULL + ed_last_error() on failure */
 const ed_call* ed_batch_calls(const ed_batch* batch);  /* device array, length ed_batch_n_calls(); call that first: it
                                                          * also re-sizes the table if the run produced more calls than
                                                          * the batch had provisioned */
