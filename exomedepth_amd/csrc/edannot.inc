@@ -252,23 +252,18 @@ struct ed_annot {
   int64_t n = 0;
   int32_t n_chrom = 0;
   bool has_group = false, has_kind = false;
-  hipStream_t stream = nullptr;
-  char* d_track = nullptr;    // ONE allocation: start, end, pmax, index, group, kind (int32 [n] each), then chrom_off (int64 [n_chrom + 1])
+  DevBuf<char> d_track;       // ONE allocation: start, end, pmax, index, group, kind (int32 [n] each), then chrom_off (int64 [n_chrom + 1])
   AnnotTrack track{};
-  char* d_work = nullptr;     // ONE grow-only allocation for a query set's arrays (carved in ed_annot_overlaps)
-  size_t work_bytes = 0;
-  int32_t* d_hits = nullptr;  // grow-only
-  int64_t hits_cap = 0;
+  DevBuf<char> d_work;        // ONE grow-only allocation for a query set's arrays (carved in ed_annot_overlaps)
+  DevBuf<int32_t> d_hits;     // grow-only
+  Stream stream;              // (declared last: it goes first, after ed_annot_destroy has waited for it)
 };
 
 ED_EXPORT void ed_annot_destroy(ed_annot* a)
 {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->stream) { (void)hipStreamSynchronize(a->stream); (void)hipStreamDestroy(a->stream); }
-  if (a->d_track) (void)hipFree(a->d_track);
-  if (a->d_work) (void)hipFree(a->d_work);
-  if (a->d_hits) (void)hipFree(a->d_hits);
+  if (a->stream) (void)hipStreamSynchronize(a->stream);
   delete a;
 }
 
@@ -335,13 +330,16 @@ try {
   for (int32_t c = 0; c <= n_chrom; ++c) h_off[c] = off[c];
   ed_annot* a = new (std::nothrow) ed_annot;
   if (!a) return ed_fail(ED_ERR_NOMEM, "out of host memory");
-  struct Guard { ed_annot* a; ~Guard() { if (a) ed_annot_destroy(a); } } guard{a};   // released on success only
+  struct Guard { ed_annot* a; ~Guard() { if (a) ed_annot_destroy(a); } } guard{a};   // released on success only (ed_annot_destroy waits for the stream)
   a->device = device; a->n = n; a->n_chrom = n_chrom; a->has_group = group != nullptr; a->has_kind = kind != nullptr;
-  if (hipMalloc((void**)&a->d_track, bytes) != hipSuccess) {
-    a->d_track = nullptr;
+  if (a->d_track.alloc(bytes) != hipSuccess) {
     return ed_fail(ED_ERR_NOMEM, "ed_annot_create: device allocation of %zu bytes failed", bytes);
   }
-  HIP_TRY(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
+  {
+    hipStream_t st = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    a->stream.reset(st);
+  }
   HIP_TRY(hipMemcpyAsync(a->d_track, img.data(), bytes, hipMemcpyHostToDevice, a->stream));
   HIP_TRY(hipStreamSynchronize(a->stream));
   char* d = a->d_track;
@@ -384,14 +382,8 @@ try {
   const int64_t nb = (n_q + kAnnotScanBlock - 1) / kAnnotScanBlock;
   const size_t a4 = annot_up((size_t)n_q * 4), a8 = annot_up(((size_t)n_q + 1) * 8), ab = annot_up((size_t)nb * 8);
   const size_t need = 8 * a4 + 2 * a8 + ab + 256;
-  if (need > a->work_bytes) {
-    if (a->d_work) { (void)hipFree(a->d_work); a->d_work = nullptr; a->work_bytes = 0; }
-    if (hipMalloc((void**)&a->d_work, need) != hipSuccess) {
-      a->d_work = nullptr;
-      return ed_fail(ED_ERR_NOMEM, "ed_annot_overlaps: device allocation of %zu bytes failed", need);
-    }
-    a->work_bytes = need;
-  }
+  if (a->d_work.reserve(need) != hipSuccess)
+    return ed_fail(ED_ERR_NOMEM, "ed_annot_overlaps: device allocation of %zu bytes failed", need);
   char* w = a->d_work;
   int32_t* d_qc = (int32_t*)w;
   int32_t* d_qs = (int32_t*)(w + a4);
@@ -433,14 +425,8 @@ try {
     return ed_fail(ED_ERR_INVALID, "ed_annot_overlaps: %lld hits do not fit cap = %lld; hits needs room for %lld entries (nothing was written to it)",
                    (long long)total, (long long)cap, (long long)total);
   if (total == 0) return ED_OK;
-  if (total > a->hits_cap) {
-    if (a->d_hits) { (void)hipFree(a->d_hits); a->d_hits = nullptr; a->hits_cap = 0; }
-    if (hipMalloc((void**)&a->d_hits, (size_t)total * 4) != hipSuccess) {
-      a->d_hits = nullptr;
-      return ed_fail(ED_ERR_NOMEM, "ed_annot_overlaps: device allocation of %zu bytes for the hits failed", (size_t)total * 4);
-    }
-    a->hits_cap = total;
-  }
+  if (a->d_hits.reserve((size_t)total * 4) != hipSuccess)
+    return ed_fail(ED_ERR_NOMEM, "ed_annot_overlaps: device allocation of %zu bytes for the hits failed", (size_t)total * 4);
   hipLaunchKernelGGL(k_annot_fill, dim3(grid_q), dim3(kAnnotBlock), 0, st, a->track, Q, min_overlap, d_lo, d_wn, d_offsets, a->d_hits);
   hipLaunchKernelGGL(k_annot_fill_wide, dim3(grid_w), dim3(kAnnotBlock), 0, st, a->track, Q, min_overlap, d_lo, d_wn, d_list, d_nwide, d_offsets, a->d_hits);
   HIP_TRY(hipGetLastError());

@@ -769,7 +769,7 @@ static int bins_count_undone(const int* d_done, int64_t S, hipStream_t st, int64
 //                          converged in the passes issued; an empty level is the reference's stop("Binning did not happen properly")
 void fit_bins_hist_passes(ed_batch* b, int B, const double* d_edges, hipStream_t st, int n)
 {
-  BinsWork& w = *(BinsWork*)b->binsw;
+  BinsWork& w = *b->binsw;
   const int64_t S = b->S;
   const dim3 gq((unsigned)((S + kLhS - 1) / kLhS)), bq(kLhS, kLhY);
   const dim3 gred((unsigned)((S + kWave - 1) / kWave)), bred(kWave, kRedY);
@@ -782,11 +782,11 @@ void fit_bins_hist_passes(ed_batch* b, int B, const double* d_edges, hipStream_t
 
 int fit_bins_hist_results(ed_batch* b, int B, hipStream_t st)
 {
-  BinsWork& w = *(BinsWork*)b->binsw;
+  BinsWork& w = *b->binsw;
   const int64_t S = b->S;
-  int* h_flags = (int*)w.host;
+  int* h_flags = w.host.as<int>();
   int* h_done = h_flags + 1;
-  double* h_pop = (double*)((char*)w.host + ((4 + (size_t)S * 4 + 7) / 8) * 8);
+  double* h_pop = (double*)(w.host.as<char>() + ((4 + (size_t)S * 4 + 7) / 8) * 8);
   HIP_TRY(hipMemcpyAsync(h_flags, w.flags, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(h_done, w.done, (size_t)S * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(h_pop, w.pop, (size_t)B * S * 8, hipMemcpyDeviceToHost, st));
@@ -803,16 +803,12 @@ int fit_bins_hist_issue(ed_batch* b, const int32_t* d_test, const int32_t* d_ref
   const int64_t lo = (int64_t)std::floor(index), hi = (int64_t)std::ceil(index);
   const double h = index - (double)lo;
   if (!b->binsw) {
-    b->binsw = new (std::nothrow) BinsWork;
+    b->binsw.reset(new (std::nothrow) BinsWork);
     if (!b->binsw) return ed_fail(ED_ERR_NOMEM, "out of host memory");
   }
-  BinsWork& w = *(BinsWork*)b->binsw;
+  BinsWork& w = *b->binsw;
   if (int rc = w.alloc(E, S, B)) return rc;
-  if (!b->fitw) {
-    b->fitw = new (std::nothrow) FitWork;
-    if (!b->fitw) return ed_fail(ED_ERR_NOMEM, "out of host memory");
-    if (int rc = b->fitw->alloc(E, S)) return rc;
-  }
+  if (int rc = batch_fitwork(b, E, S)) return rc;
   FitWork& fw = *b->fitw;
   const dim3 g1((unsigned)((S + 255) / 256)), b1(256);
   const dim3 gq((unsigned)((S + kLhS - 1) / kLhS)), bq(kLhS, kLhY);
@@ -850,12 +846,12 @@ int fit_bins_hist_issue(ed_batch* b, const int32_t* d_test, const int32_t* d_ref
 
 int fit_bins_hist_status(ed_batch* b, int B, int* status)
 {
-  BinsWork& w = *(BinsWork*)b->binsw;
+  BinsWork& w = *b->binsw;
   const int64_t S = b->S;
   HIP_TRY(hipEventSynchronize(w.ev));
-  const int* h_flags = (const int*)w.host;
+  const int* h_flags = w.host.as<const int>();
   const int* h_done = h_flags + 1;
-  const double* h_pop = (const double*)((const char*)w.host + ((4 + (size_t)S * 4 + 7) / 8) * 8);
+  const double* h_pop = (const double*)(w.host.as<const char>() + ((4 + (size_t)S * 4 + 7) / 8) * 8);
   *status = 0;
   if (*h_flags) { *status = 1; return ED_OK; }   // not this form's data
   for (int64_t s = 0; s < S; ++s)
@@ -878,7 +874,7 @@ int fit_bins_hist(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, int 
   if (int rc = fit_bins_hist_status(b, B, &status)) return rc;
   if (status == 1) return ED_OK;
   if (status == 2) fit_bins_hist_passes(b, B, d_edges, st, 28);
-  BinsWork& w = *(BinsWork*)b->binsw;
+  BinsWork& w = *b->binsw;
   hipLaunchKernelGGL(k_fitb_finish, dim3((unsigned)((b->S + 255) / 256)), dim3(256), 0, st, w.eta, w.lam, B, b->S, d_phi_bins, d_expected);
   HIP_TRY(hipGetLastError());
   b->bins_unconverged = 0;
@@ -889,12 +885,9 @@ int fit_bins_hist(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, int 
 
 }  // namespace
 
-static void binswork_free(void* w)
-{
-  if (!w) return;
-  ((BinsWork*)w)->release();
-  delete (BinsWork*)w;
-}
+// Both workspace types are complete here.  The members go in reverse order of declaration: the workspaces, every buffer and event, the
+// streams last (see the struct).
+ed_batch::~ed_batch() = default;
 
 ED_EXPORT int ed_batch_fit_bins(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, int phi_bins, double* d_phi_bins,
                                 double* d_edges, double* d_expected, void* stream_)
@@ -931,7 +924,7 @@ try {
       return ED_OK;
     }
   }
-  DevBuf dpart, dred, di32, deta, dlam, ddone, dpop, dstate;
+  DevBuf<void> dpart, dred, di32, deta, dlam, ddone, dpop, dstate;
   HIP_TRY(dpart.alloc((size_t)nchunk * 6 * B * S * 8));
   HIP_TRY(dred.alloc((size_t)kRsQ * S * 8));
   HIP_TRY(di32.alloc((size_t)7 * S * 4));
@@ -946,7 +939,7 @@ try {
   int32_t* xmax = mid1 + S;
   // the column maxima (= quantile(., 1)) first: they bound the bisection, which then needs ceil(log2(max + 1))
   // counting passes instead of 32
-  DevBuf dpmax;
+  DevBuf<void> dpmax;
   HIP_TRY(dpmax.alloc((size_t)nchunk * S * 4));
   hipLaunchKernelGGL(k_bins_colmax, gcol, bcol, 0, st, d_ref, E, S, dpmax.as<int32_t>(), (const int*)nullptr, (int64_t)1);
   hipLaunchKernelGGL(k_bins_max_reduce, g1, b1, 0, st, dpmax.as<int32_t>(), nchunk, S, xmax);
@@ -976,7 +969,7 @@ try {
   {
     // R/class_definition.R:130-133: every level of depth.quant must be populated
     std::vector<double> pop((size_t)B * S);
-    HIP_TRY(hipMemcpyAsync(pop.data(), dpop.p, pop.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pop.data(), dpop.get(), pop.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int64_t s = 0; s < S; ++s)
       for (int g = 0; g < B; ++g)
@@ -986,11 +979,7 @@ try {
   }
   // start from the converged single-dispersion fit (histogram form, ~1.6 ms): the levels' dispersions are corrections
   {
-    if (!b->fitw) {
-      b->fitw = new (std::nothrow) FitWork;
-      if (!b->fitw) return ed_fail(ED_ERR_NOMEM, "out of host memory");
-      if (int rc = b->fitw->alloc(E, S)) return rc;
-    }
+    if (int rc = batch_fitwork(b, E, S)) return rc;
     FitWork& w = *b->fitw;
     // (d_phi_bins' first row and d_expected serve as scratch outputs of the plain fit; both are rewritten below)
     if (int rc = fit_columns(w, d_test, S, 1, d_ref, S, E, S, d_phi_bins, d_expected, st, true)) return rc;
@@ -1078,7 +1067,7 @@ static int batch_run_bins_skip(ed_batch* b, const int32_t* d_test, const int32_t
 {
   EmitModel em;
   em.bins = phi_bins; em.edges = d_edges;
-  em.skip = b->binsw ? ((BinsWork*)b->binsw)->flags : nullptr;
+  em.skip = b->binsw ? b->binsw->flags.get() : nullptr;
   return batch_run_impl(b, d_test, d_ref, d_phi_bins, d_expected, mixture, (void*)st, em);
 }
 

@@ -476,46 +476,38 @@ k_lh_newton(const uint32_t* __restrict__ lhist, const uint32_t* __restrict__ rhi
 // device buffers of the histogram form, kept on the batch (hipFree would synchronise the device on every fit)
 struct BinsWork {
   int64_t E = 0, S = 0; int B = 0;
-  uint32_t *rhist = nullptr, *lhist = nullptr, *beyond = nullptr;
-  int32_t *xmax = nullptr, *x0 = nullptr, *x1 = nullptr, *ov_y = nullptr, *ov_r = nullptr, *ovn = nullptr;
-  int2* sorted = nullptr;
-  int *lvl_start = nullptr, *flags = nullptr, *done = nullptr;
-  double *pop = nullptr, *eta = nullptr, *lam = nullptr, *state = nullptr, *part = nullptr;
-  void* host = nullptr;   // pinned: flags (1 int), done (S ints), pop (kMaxPhiBins x S doubles)
-  hipEvent_t ev = nullptr;   // the three copies into `host` of the last fit are complete
-  void release()
-  {
-    void* ptrs[] = {rhist, lhist, beyond, xmax, x0, x1, ov_y, ov_r, ovn, sorted, lvl_start, flags, done, pop, eta, lam, state, part};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (host) (void)hipHostFree(host);
-    if (ev) (void)hipEventDestroy(ev);
-    *this = BinsWork();
-  }
+  DevBuf<uint32_t> rhist, lhist, beyond;
+  DevBuf<int32_t> xmax, x0, x1, ov_y, ov_r, ovn;
+  DevBuf<int2> sorted;
+  DevBuf<int> lvl_start, flags, done;
+  DevBuf<double> pop, eta, lam, state, part;
+  PinBuf<void> host;   // pinned: flags (1 int), done (S ints), pop (kMaxPhiBins x S doubles)
+  Event ev;            // the three copies into `host` of the last fit are complete
   int alloc(int64_t E_, int64_t S_, int B_)
   {
     if (E_ == E && S_ == S && B_ <= B) return ED_OK;
-    release();
+    *this = BinsWork();
     const int64_t Sp = lh_padded(S_);
-    HIP_TRY(hipMalloc((void**)&rhist, (size_t)kLhHalves * Sp * kLhKq * 4));
-    HIP_TRY(hipMalloc((void**)&lhist, (size_t)kLhHalves * Sp * B_ * kLhK * 4));
-    HIP_TRY(hipMalloc((void**)&beyond, (size_t)S_ * 4));
-    HIP_TRY(hipMalloc((void**)&xmax, (size_t)S_ * 4));
-    HIP_TRY(hipMalloc((void**)&x0, (size_t)S_ * 4));
-    HIP_TRY(hipMalloc((void**)&x1, (size_t)S_ * 4));
-    HIP_TRY(hipMalloc((void**)&ov_y, (size_t)kLhListTotal * S_ * 4));
-    HIP_TRY(hipMalloc((void**)&ov_r, (size_t)kLhListTotal * S_ * 4));
-    HIP_TRY(hipMalloc((void**)&ovn, (size_t)(kLhHalves * kLhBlock) * S_ * 4));
-    HIP_TRY(hipMalloc((void**)&sorted, (size_t)kLhListTotal * S_ * 8));
-    HIP_TRY(hipMalloc((void**)&lvl_start, (size_t)(kMaxPhiBins + 1) * S_ * 4));
-    HIP_TRY(hipMalloc((void**)&flags, 4));
-    HIP_TRY(hipMalloc((void**)&done, (size_t)S_ * 4));
-    HIP_TRY(hipMalloc((void**)&pop, (size_t)kMaxPhiBins * S_ * 8));
-    HIP_TRY(hipMalloc((void**)&eta, (size_t)S_ * 8));
-    HIP_TRY(hipMalloc((void**)&lam, (size_t)kMaxPhiBins * S_ * 8));
-    HIP_TRY(hipMalloc((void**)&state, (size_t)(2 * (kMaxPhiBins + 1) + 2) * S_ * 8));
-    HIP_TRY(hipMalloc((void**)&part, (size_t)6 * kMaxPhiBins * S_ * 8));
-    HIP_TRY(hipHostMalloc(&host, 4 + (size_t)S_ * 4 + 4 + (size_t)kMaxPhiBins * S_ * 8));
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIP_TRY(rhist.alloc((size_t)kLhHalves * Sp * kLhKq * 4));
+    HIP_TRY(lhist.alloc((size_t)kLhHalves * Sp * B_ * kLhK * 4));
+    HIP_TRY(beyond.alloc((size_t)S_ * 4));
+    HIP_TRY(xmax.alloc((size_t)S_ * 4));
+    HIP_TRY(x0.alloc((size_t)S_ * 4));
+    HIP_TRY(x1.alloc((size_t)S_ * 4));
+    HIP_TRY(ov_y.alloc((size_t)kLhListTotal * S_ * 4));
+    HIP_TRY(ov_r.alloc((size_t)kLhListTotal * S_ * 4));
+    HIP_TRY(ovn.alloc((size_t)(kLhHalves * kLhBlock) * S_ * 4));
+    HIP_TRY(sorted.alloc((size_t)kLhListTotal * S_ * 8));
+    HIP_TRY(lvl_start.alloc((size_t)(kMaxPhiBins + 1) * S_ * 4));
+    HIP_TRY(flags.alloc(4));
+    HIP_TRY(done.alloc((size_t)S_ * 4));
+    HIP_TRY(pop.alloc((size_t)kMaxPhiBins * S_ * 8));
+    HIP_TRY(eta.alloc((size_t)S_ * 8));
+    HIP_TRY(lam.alloc((size_t)kMaxPhiBins * S_ * 8));
+    HIP_TRY(state.alloc((size_t)(2 * (kMaxPhiBins + 1) + 2) * S_ * 8));
+    HIP_TRY(part.alloc((size_t)6 * kMaxPhiBins * S_ * 8));
+    HIP_TRY(host.alloc(4 + (size_t)S_ * 4 + 4 + (size_t)kMaxPhiBins * S_ * 8));
+    HIP_TRY(ev.create(hipEventDisableTiming));
     E = E_; S = S_; B = B_;
     return ED_OK;
   }

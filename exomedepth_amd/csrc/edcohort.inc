@@ -154,8 +154,8 @@ struct ed_stager {
   ~ed_stager() { if (getenv("ED_STAGE_TIMING")) fprintf(stderr, "[stager] narrow: %lld chunks, waiting for a buffer %.1f ms, converting %.1f ms\n", (long long)dbg_chunks, dbg_wait * 1e3, dbg_conv * 1e3); }
   ed_stage_workers workers;
   size_t chunk = 0;
-  void* pin[2] = {nullptr, nullptr};
-  hipEvent_t freed[2] = {nullptr, nullptr};   // the DMA that last read pin[i] is complete
+  PinBuf<void> pin[2];
+  Event freed[2];                             // the DMA that last read pin[i] is complete
   bool used[2] = {false, false};
   int next = 0;
   int n_threads = 4;
@@ -163,19 +163,9 @@ struct ed_stager {
   double bytes = 0, seconds_host = 0;
 };
 
-static void stager_free(ed_stager* g)
+static int stager_make(std::unique_ptr<ed_stager>& out, int device, size_t chunk_bytes)
 {
-  if (!g) return;
-  for (int i = 0; i < 2; ++i) {
-    if (g->pin[i]) (void)hipHostFree(g->pin[i]);
-    if (g->freed[i]) (void)hipEventDestroy(g->freed[i]);
-  }
-  delete g;
-}
-
-static int stager_make(ed_stager** out, int device, size_t chunk_bytes)
-{
-  ed_stager* g = new (std::nothrow) ed_stager;
+  std::unique_ptr<ed_stager> g(new (std::nothrow) ed_stager);
   if (!g) return ed_fail(ED_ERR_NOMEM, "out of host memory");
   g->device = device;
   g->chunk = std::max<size_t>(chunk_bytes, 1 << 20);
@@ -206,15 +196,25 @@ static int stager_make(ed_stager** out, int device, size_t chunk_bytes)
   }
   g->workers.start(g->n_threads);
   for (int i = 0; i < 2; ++i) {
-    if (hipHostMalloc(&g->pin[i], g->chunk, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&g->freed[i], hipEventDisableTiming) != hipSuccess) {
-      stager_free(g);
+    if (g->pin[i].alloc(g->chunk) != hipSuccess || g->freed[i].create(hipEventDisableTiming) != hipSuccess)
       return ed_fail(ED_ERR_NOMEM, "ingest: cannot allocate %zu bytes of pinned staging memory", chunk_bytes);
-    }
   }
-  *out = g;
+  out = std::move(g);
   return ED_OK;
 }
+
+// The stream and the stager of one host-fed call.  Declared after the call's device buffers, so that it goes before them: the stream
+// is waited for, then destroyed, then the stager goes.
+struct HostFeed {
+  std::unique_ptr<ed_stager> g;
+  Stream s;
+  int open(int dev)
+  {
+    HIP_TRY(ed_stream_create(s, false, dev));
+    return stager_make(g, dev, (size_t)64 << 20);
+  }
+  ~HostFeed() { if (s) (void)hipStreamSynchronize(s); }
+};
 
 static bool host_block_is_pinned(const void* p)
 {
@@ -246,7 +246,7 @@ static int stager_upload(ed_stager* g, const void* src, size_t rows, size_t row_
         nbytes = std::min(g->chunk, total - done_bytes);
         const char* s0 = (const char*)src + done_bytes;
         const int nt = (nbytes >= ((size_t)4 << 20)) ? g->n_threads : 1;
-        char* const dstp = (char*)g->pin[i];
+        char* const dstp = g->pin[i].as<char>();
         g->workers.run([=](int t) {
           const size_t a = nbytes * (size_t)t / nt, z = nbytes * (size_t)(t + 1) / nt;
           std::memcpy(dstp + a, s0 + a, z - a);
@@ -256,7 +256,7 @@ static int stager_upload(ed_stager* g, const void* src, size_t rows, size_t row_
         nbytes = nr * row_bytes;
         const char* s0 = (const char*)src + done_rows * src_pitch;
         const int nt = (nbytes >= ((size_t)4 << 20)) ? g->n_threads : 1;
-        char* const dstp = (char*)g->pin[i];
+        char* const dstp = g->pin[i].as<char>();
         g->workers.run([=](int t) {
           const size_t a = nr * (size_t)t / nt, z = nr * (size_t)(t + 1) / nt;
           for (size_t r = a; r < z; ++r) std::memcpy(dstp + r * row_bytes, s0 + r * src_pitch, row_bytes);
@@ -293,7 +293,7 @@ static int stager_upload_narrow(ed_stager* g, const int32_t* src, size_t count, 
     g->dbg_wait += std::chrono::duration<double>(tw1 - tw0).count();
     const size_t n = std::min(per, count - done);
     const int32_t* s0 = src + done;
-    uint16_t* p = (uint16_t*)g->pin[i];
+    uint16_t* p = g->pin[i].as<uint16_t>();
     const int nt = (n >= ((size_t)1 << 20)) ? g->n_threads : 1;
     std::vector<uint32_t> seen((size_t)nt, 0u);
     uint32_t* const seenp = seen.data();
@@ -340,34 +340,34 @@ struct ed_cohort {
   int64_t slab = 0;
   int n_slots = 0;
   struct Slot {
-    ed_batch* batch = nullptr;       // sized for the nominal slab
-    ed_batch* odd = nullptr;         // sized for a ragged slab (made when one is submitted)
-    ed_batch* cur = nullptr;         // the one that holds the slot's current ticket
-    double* d_phi = nullptr;         // [slab] (phi, expected) of the slot's ticket: fitted here, or copied from the caller's
-    double* d_exp = nullptr;
-    hipEvent_t emitted = nullptr;    // main stream: the emission kernels of the slot's last run are through
-    hipEvent_t fitted = nullptr;     // fit stream: the slot's (phi, expected) are complete
-    hipEvent_t ready = nullptr;      // the slab's counts are complete on the caller's / the copy stream
+    std::unique_ptr<ed_batch> batch; // sized for the nominal slab
+    std::unique_ptr<ed_batch> odd;   // sized for a ragged slab (made when one is submitted)
+    ed_batch* cur = nullptr;         // borrowed: the one of the two that holds the slot's current ticket
+    DevBuf<double> d_phi, d_exp;     // [slab] (phi, expected) of the slot's ticket: fitted here, or copied from the caller's
+    Event emitted;                   // main stream: the emission kernels of the slot's last run are through
+    Event fitted;                    // fit stream: the slot's (phi, expected) are complete
+    Event ready;                     // the slab's counts are complete on the caller's / the copy stream
     bool emitted_set = false;
     int64_t ticket = -1;
     int64_t n = 0;
     // host-fed slabs (ed_cohort_run_host / ed_cohort_submit_host): counts owned by the slot
-    int32_t* own_test = nullptr;
-    int32_t* own_ref = nullptr;
-    void* raw = nullptr;             // staging for the layouts that need a device pass (2 matrices)
-    size_t raw_bytes = 0;
-    uint8_t* path_cols = nullptr;    // [n][E] copy of the path for the column-major output
+    DevBuf<int32_t> own_test, own_ref;
+    DevBuf<char> raw;                // staging for the layouts that need a device pass (2 matrices)
+    DevBuf<uint8_t> path_cols;       // [n][E] copy of the path for the column-major output
     // depth-binned dispersion (option phi_bins > 1): phi.estimates [8][slab] and complete.bins [9][slab] of the slot's ticket; the
     // fit is issued without a look at its outcome, which is settled when the ticket is first waited for (cohort_bins_settle)
-    double* d_phib = nullptr;
-    double* d_edges = nullptr;
+    DevBuf<double> d_phib, d_edges;
     bool bins_pending = false;
-    const int32_t* last_test = nullptr;
+    const int32_t* last_test = nullptr;   // borrowed: the counts of the slot's ticket (the caller's, or own_test / own_ref)
     const int32_t* last_ref = nullptr;
     double last_mix = 1.0;
     const double* last_mix_s = nullptr;   // ... and its per-sample mixtures (ed_cohort_submit_mix), if any
     int lane = 0;
   };
+  // (declared ahead of the slots, the stager and the buffers: members go in reverse order, so the streams outlive everything queued on them)
+  static constexpr int kMaxLanes = 4;
+  Stream mains[kMaxLanes], fits[kMaxLanes];
+  Stream copy;
   std::vector<Slot> slots;
   // LANES (round 5): independent pipelines inside one cohort object.  Slot s belongs to lane s % n_lanes; a lane has its own emission ("main") and fit
   // streams and its slots' batch objects their own side / tail streams, so nothing orders the slabs of different lanes against each other.  Why: one
@@ -379,15 +379,12 @@ struct ed_cohort {
   // fills the chip and is fitted on the device (the bench's headline: 3.9 against 4.2 ms); measured WORSE for 64-sample slabs with given parameters
   // (six slabs in flight as three lanes: 1.56 ms per slab against 0.66 as one lane -- that pipeline lives on its one fit stream running ahead) and
   // for host-fed slabs (link-bound: 21.4 against 16.1 ms).
-  static constexpr int kMaxLanes = 4;
   int n_lanes = 1, lanes_opt = 1;
-  hipStream_t mains[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr}, fits[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
-  hipStream_t copy = nullptr;
   bool pipelined() const { return n_slots / n_lanes >= 2; }     // a lane with two or more slots overlaps the stages of its consecutive slabs
   int64_t next_ticket = 0;
   bool started = false;
   bool timing = false;
-  hipEvent_t epoch = nullptr;        // option timing: recorded (and waited for) when the option is set; the emission launches' intervals are relative to it
+  Event epoch;                       // option timing: recorded (and waited for) when the option is set; the emission launches' intervals are relative to it
   std::vector<float> emit_iv;        // (start_ms, end_ms) of the emission stage of every timed run, in the order the runs were folded
   // options
   double split_frac = 0.30;
@@ -408,11 +405,9 @@ struct ed_cohort {
   bool tables_early = false;         // per-sample constants and tables of a slab right behind its fit, on the fit stream (measured:
                                      // the boundary between two emission launches shrinks by 0.3 ms and the launch that hosts them grows
                                      // by as much -- 10.26-10.41 against 10.27-10.35 ms per step -- so the default keeps them at the boundary)
-  ed_stager* stager = nullptr;
-  double* d_par = nullptr;           // ed_cohort_run_host with given parameters: (phi[S_total], expected[S_total]) on the device
-  int64_t par_cap = 0;
-  double* d_mixv = nullptr;          // ed_cohort_run_host_mix: the per-sample mixtures [S_total] on the device
-  int64_t mixv_cap = 0;
+  std::unique_ptr<ed_stager> stager;
+  DevBuf<double> d_par;              // ed_cohort_run_host with given parameters: (phi[S_total], expected[S_total]) on the device; grow-only
+  DevBuf<double> d_mixv;             // ed_cohort_run_host_mix: the per-sample mixtures [S_total] on the device; grow-only
   // results of ed_cohort_run_host
   std::vector<ed_call> calls;
   std::vector<ed_call_info> info;
@@ -420,29 +415,6 @@ struct ed_cohort {
   int64_t n_gsl_errors = 0;
   int64_t tab_stats[4] = {0, 0, 0, 0};   // ed_batch_table_stats summed over the slabs of the last ed_cohort_run_host
 };
-
-static void cohort_free(ed_cohort* c)
-{
-  if (!c) return;
-  for (auto& sl : c->slots) {
-    if (sl.batch) ed_batch_destroy(sl.batch);
-    if (sl.odd) ed_batch_destroy(sl.odd);
-    void* ptrs[] = {sl.d_phi, sl.d_exp, sl.own_test, sl.own_ref, sl.raw, sl.path_cols, sl.d_phib, sl.d_edges};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    hipEvent_t evs[] = {sl.emitted, sl.fitted, sl.ready};
-    for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-  }
-  if (c->stager) stager_free(c->stager);
-  if (c->epoch) (void)hipEventDestroy(c->epoch);
-  if (c->d_par) (void)hipFree(c->d_par);
-  if (c->d_mixv) (void)hipFree(c->d_mixv);
-  for (int l = 0; l < ed_cohort::kMaxLanes; ++l) {
-    if (c->mains[l]) (void)hipStreamDestroy(c->mains[l]);
-    if (c->fits[l]) (void)hipStreamDestroy(c->fits[l]);
-  }
-  if (c->copy) (void)hipStreamDestroy(c->copy);
-  delete c;
-}
 
 ED_EXPORT int ed_cohort_create(ed_cohort** cohort, ed_plan* plan, int64_t slab_samples, int slabs_in_flight)
 try {
@@ -464,14 +436,14 @@ ED_EXPORT void ed_cohort_destroy(ed_cohort* c)
   if (!c) return;
   (void)hipSetDevice(c->plan->device);
   (void)hipDeviceSynchronize();
-  cohort_free(c);
+  delete c;
 }
 
 // the reference point of the emission intervals: an event that has completed, on the cohort's device
 static int cohort_epoch(ed_cohort* c)
 {
   HIP_TRY(hipSetDevice(c->plan->device));
-  if (!c->epoch) HIP_TRY(hipEventCreate(&c->epoch));
+  if (!c->epoch) HIP_TRY(c->epoch.create());
   HIP_TRY(hipEventRecord(c->epoch, c->mains[0]));
   HIP_TRY(hipEventSynchronize(c->epoch));
   return ED_OK;
@@ -486,10 +458,10 @@ try {
     c->emit_iv.clear();
     if (c->timing && c->started) { if (int rc = cohort_epoch(c)) return rc; }
     for (auto& sl : c->slots) {
-      for (ed_batch* b : {sl.batch, sl.odd}) {
+      for (ed_batch* b : {sl.batch.get(), sl.odd.get()}) {
         if (!b) continue;
         ed_batch_enable_timing(b, c->timing);
-        b->epoch = c->timing ? c->epoch : nullptr; b->emit_iv = c->timing ? &c->emit_iv : nullptr;
+        b->epoch = c->timing ? c->epoch.get() : nullptr; b->emit_iv = c->timing ? &c->emit_iv : nullptr;
       }
     }
     return ED_OK;
@@ -532,6 +504,14 @@ try {
 }
 ED_CATCH("ed_cohort_set_option")
 
+static int batch_make(std::unique_ptr<ed_batch>& out, ed_plan* plan, int64_t n)
+{
+  ed_batch* b = nullptr;
+  if (int rc = ed_batch_create(&b, plan, n)) return rc;
+  out.reset(b);
+  return ED_OK;
+}
+
 // streams, slot buffers and the nominal batch objects: on the first submission, in a fixed order
 static int cohort_start(ed_cohort* c)
 {
@@ -544,29 +524,28 @@ static int cohort_start(ed_cohort* c)
   // (every resource is made only if it is not there yet: a start that failed half-way -- device memory -- is taken up where it stopped by the next
   // submission instead of making the streams, batch objects and buffers it already has a second time)
   for (int l = 0; l < c->n_lanes; ++l) {
-    if (!c->mains[l]) HIP_TRY(ed_stream_create(&c->mains[l], c->own_queues, dev));
-    if (pipelined && !c->fits[l]) HIP_TRY(ed_stream_create(&c->fits[l], c->own_queues, dev));
+    if (!c->mains[l]) HIP_TRY(ed_stream_create(c->mains[l], c->own_queues, dev));
+    if (pipelined && !c->fits[l]) HIP_TRY(ed_stream_create(c->fits[l], c->own_queues, dev));
   }
   for (size_t i = 0; i < c->slots.size(); ++i) c->slots[i].lane = (int)(i % (size_t)c->n_lanes);
   for (auto& sl : c->slots) {
     if (!sl.batch) {
-      if (int rc = ed_batch_create(&sl.batch, c->plan, c->slab)) return rc;
+      if (int rc = batch_make(sl.batch, c->plan, c->slab)) return rc;
       if (c->own_queues && !sl.batch->sides.empty()) {   // the stream the chains run on (single-group mode uses the first side stream only)
-        hipStream_t own = nullptr;
-        HIP_TRY(ed_stream_create(&own, true, dev));
-        (void)hipStreamDestroy(sl.batch->sides[0]);
-        sl.batch->sides[0] = own;
+        Stream own;
+        HIP_TRY(ed_stream_create(own, true, dev));
+        sl.batch->replace_side(0, std::move(own));
       }
     }
-    if (!sl.d_phi) HIP_TRY(hipMalloc((void**)&sl.d_phi, (size_t)c->slab * 8));
-    if (!sl.d_exp) HIP_TRY(hipMalloc((void**)&sl.d_exp, (size_t)c->slab * 8));
+    if (!sl.d_phi) HIP_TRY(sl.d_phi.alloc((size_t)c->slab * 8));
+    if (!sl.d_exp) HIP_TRY(sl.d_exp.alloc((size_t)c->slab * 8));
     if (c->phi_bins > 1) {
-      if (!sl.d_phib) HIP_TRY(hipMalloc((void**)&sl.d_phib, (size_t)kMaxPhiBins * c->slab * 8));
-      if (!sl.d_edges) HIP_TRY(hipMalloc((void**)&sl.d_edges, (size_t)(kMaxPhiBins + 1) * c->slab * 8));
+      if (!sl.d_phib) HIP_TRY(sl.d_phib.alloc((size_t)kMaxPhiBins * c->slab * 8));
+      if (!sl.d_edges) HIP_TRY(sl.d_edges.alloc((size_t)(kMaxPhiBins + 1) * c->slab * 8));
     }
-    if (!sl.emitted) HIP_TRY(hipEventCreateWithFlags(&sl.emitted, hipEventDisableTiming));
-    if (!sl.fitted) HIP_TRY(hipEventCreateWithFlags(&sl.fitted, hipEventDisableTiming));
-    if (!sl.ready) HIP_TRY(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
+    if (!sl.emitted) HIP_TRY(sl.emitted.create(hipEventDisableTiming));
+    if (!sl.fitted) HIP_TRY(sl.fitted.create(hipEventDisableTiming));
+    if (!sl.ready) HIP_TRY(sl.ready.create(hipEventDisableTiming));
   }
   c->started = true;
   return ED_OK;
@@ -582,7 +561,7 @@ static int cohort_adopt(ed_cohort* c, ed_batch* b)
     if (int rc = ed_batch_set_viterbi_overlap(b, c->viterbi_overlap)) return rc;
     // (emit mode 2: no cut -- the sample-major fit's workgroups are small, the next slab's fit is issued as soon as its stream is free)
     if (!c->viterbi_overlap && c->split_frac > 0.0 && !(c->emit_mode == 2 && !c->split_set)) {
-      if (!b->split_ev) HIP_TRY(hipEventCreateWithFlags(&b->split_ev, hipEventDisableTiming));
+      if (!b->split_ev) HIP_TRY(b->split_ev.create(hipEventDisableTiming));
       b->split_frac = c->split_frac;
     }
   }
@@ -598,7 +577,7 @@ static int cohort_adopt(ed_cohort* c, ed_batch* b)
   b->bins_pieces = (pipelined && c->phi_bins > 1) ? c->bins_pieces : 1;
   if (c->timing && !b->timing) ed_batch_enable_timing(b, 1);   // (enabling resets the sums: once per batch object)
   if (c->timing && !c->epoch) { if (int rc = cohort_epoch(c)) return rc; }
-  b->epoch = c->timing ? c->epoch : nullptr; b->emit_iv = c->timing ? &c->emit_iv : nullptr;
+  b->epoch = c->timing ? c->epoch.get() : nullptr; b->emit_iv = c->timing ? &c->emit_iv : nullptr;
   return ED_OK;
 }
 
@@ -642,14 +621,14 @@ static int cohort_submit(ed_cohort* c, const int32_t* d_test, const int32_t* d_r
   ed_cohort::Slot& sl = c->slots[(size_t)(t % c->n_slots)];
   if (c->phi_bins > 1 && d_phi) return ed_fail(ED_ERR_INVALID, "ed_cohort_submit: given (phi, expected) are per sample; with phi_bins > 1 the slab is fitted");
   if (int rc = cohort_bins_settle(c, sl)) return rc;   // (a ticket nobody waited for: its fit's workspace is about to be reused)
-  ed_batch* b = sl.batch;
+  ed_batch* b = sl.batch.get();
   if (n != c->slab) {
     if (sl.odd && sl.odd->S != n) {
-      if (sl.cur == sl.odd) { sl.cur = nullptr; sl.ticket = -1; }   // (the slot's last ticket dies with its batch: nothing may name it if the create below fails)
-      ed_batch_destroy(sl.odd); sl.odd = nullptr;
+      if (sl.cur == sl.odd.get()) { sl.cur = nullptr; sl.ticket = -1; }   // (the slot's last ticket dies with its batch: nothing may name it if the create below fails)
+      sl.odd.reset();
     }
-    if (!sl.odd) { if (int rc = ed_batch_create(&sl.odd, c->plan, n)) return rc; }
-    b = sl.odd;
+    if (!sl.odd) { if (int rc = batch_make(sl.odd, c->plan, n)) return rc; }
+    b = sl.odd.get();
   }
   if (int rc = cohort_adopt(c, b)) return rc;
   if (slab_bits) b->counts_bits = slab_bits;
@@ -831,7 +810,7 @@ try {
   for (int i = 0; i < 5; ++i) ms_total[i] = 0.0;
   int64_t nr = 0, nf = 0;
   for (auto& sl : c->slots) {
-    for (ed_batch* b : {sl.batch, sl.odd}) {
+    for (ed_batch* b : {sl.batch.get(), sl.odd.get()}) {
       if (!b) continue;
       double ms[5];
       int64_t r = 0, f = 0;
@@ -853,7 +832,7 @@ ED_EXPORT int ed_cohort_emission_intervals(ed_cohort* c, float* out, int64_t cap
 try {
   if (!c || !n || (cap > 0 && !out)) return ed_fail(ED_ERR_INVALID, "NULL argument");
   for (auto& sl : c->slots)
-    for (ed_batch* b : {sl.batch, sl.odd}) { if (b) { if (int rc = fold_run_times(b)) return rc; } }
+    for (ed_batch* b : {sl.batch.get(), sl.odd.get()}) { if (b) { if (int rc = fold_run_times(b)) return rc; } }
   *n = (int64_t)c->emit_iv.size() / 2;
   const int64_t k = std::min(*n, cap);
   if (k > 0) std::memcpy(out, c->emit_iv.data(), (size_t)k * 8);
@@ -867,8 +846,8 @@ try {
   if (cohort_start(c) != ED_OK) return 0;
   if (c->phi_bins > 1)   // the tabulated-constants kernel in `bins_pieces` launches (one when nothing is in flight) + the per-cell kernel for what it left
     return (c->pipelined() ? c->bins_pieces : 1) + 1;
-  if (cohort_adopt(c, c->slots[0].batch) != ED_OK) return 0;
-  return ed_batch_n_emit_launches(c->slots[0].batch);
+  if (cohort_adopt(c, c->slots[0].batch.get()) != ED_OK) return 0;
+  return ed_batch_n_emit_launches(c->slots[0].batch.get());
 }
 ED_CATCH("ed_cohort_n_emit_launches")
 
@@ -882,27 +861,24 @@ static int upload_counts(ed_stager* g, hipStream_t st, const void* host, int64_t
 static int cohort_upload_matrix(ed_cohort* c, ed_cohort::Slot& sl, const void* host, int64_t n, int layout, int wire,
                                 int64_t row_stride, int which, int32_t* d_out, int phases)
 {
-  char* raw = sl.raw ? (char*)sl.raw + (size_t)which * (sl.raw_bytes / 2) : nullptr;
+  char* raw = sl.raw ? sl.raw + (size_t)which * (sl.raw.bytes() / 2) : nullptr;
   if (c->counts_layout == 1 && layout != 1)
     return ed_fail(ED_ERR_INVALID, "host-fed slabs of a cohort with counts_layout = 1 come in layout 1 (R's column-major matrix)");
   if (c->counts_bits == 16)
     return ed_fail(ED_ERR_STATE, "option counts_bits = 16 describes device-resident slabs (ed_cohort_submit); host-fed slabs choose their device format themselves "
                                  "(uint16 whenever the counts fit and the cohort runs sample-major tables)");
-  return upload_counts(c->stager, c->copy, host, c->plan->E, n, layout, wire, row_stride, raw, d_out, phases, c->counts_layout);
+  return upload_counts(c->stager.get(), c->copy, host, c->plan->E, n, layout, wire, row_stride, raw, d_out, phases, c->counts_layout);
 }
 
 static int cohort_host_buffers(ed_cohort* c, ed_cohort::Slot& sl, bool need_raw)
 {
   const int64_t E = c->plan->E;
-  if (!c->copy) HIP_TRY(ed_stream_create(&c->copy, c->own_queues, c->plan->device));
-  if (!c->stager) { if (int rc = stager_make(&c->stager, c->plan->device, (size_t)64 << 20)) return rc; }
+  if (!c->copy) HIP_TRY(ed_stream_create(c->copy, c->own_queues, c->plan->device));
+  if (!c->stager) { if (int rc = stager_make(c->stager, c->plan->device, (size_t)64 << 20)) return rc; }
   const size_t bytes = (size_t)std::max<int64_t>(E, 1) * c->slab * 4;
-  if (!sl.own_test) HIP_TRY(hipMalloc((void**)&sl.own_test, bytes));     // (each on its own pointer: a failed second allocation is retried, not skipped)
-  if (!sl.own_ref) HIP_TRY(hipMalloc((void**)&sl.own_ref, bytes));
-  if (need_raw && !sl.raw) {
-    HIP_TRY(hipMalloc(&sl.raw, 2 * bytes));
-    sl.raw_bytes = 2 * bytes;
-  }
+  if (!sl.own_test) HIP_TRY(sl.own_test.alloc(bytes));     // (each on its own owner: a failed second allocation is retried, not skipped)
+  if (!sl.own_ref) HIP_TRY(sl.own_ref.alloc(bytes));
+  if (need_raw && !sl.raw) HIP_TRY(sl.raw.alloc(2 * bytes));
   return ED_OK;
 }
 
@@ -933,11 +909,11 @@ static int cohort_submit_host(ed_cohort* c, const void* test, const void* ref, i
     const size_t count = (size_t)c->plan->E * (size_t)n_samples;
     bool wide = false;
     if (wire == 2) {
-      if (int rc = stager_upload(c->stager, test, 1, count * 2, count * 2, sl.own_test, c->copy)) return rc;
-      if (int rc = stager_upload(c->stager, ref, 1, count * 2, count * 2, sl.own_ref, c->copy)) return rc;
+      if (int rc = stager_upload(c->stager.get(), test, 1, count * 2, count * 2, sl.own_test, c->copy)) return rc;
+      if (int rc = stager_upload(c->stager.get(), ref, 1, count * 2, count * 2, sl.own_ref, c->copy)) return rc;
     } else if (!host_block_is_pinned(test) && !host_block_is_pinned(ref)) {
-      if (int rc = stager_upload_narrow(c->stager, (const int32_t*)test, count, (uint16_t*)sl.own_test, c->copy, &wide)) return rc;
-      if (!wide) { if (int rc = stager_upload_narrow(c->stager, (const int32_t*)ref, count, (uint16_t*)sl.own_ref, c->copy, &wide)) return rc; }
+      if (int rc = stager_upload_narrow(c->stager.get(), (const int32_t*)test, count, sl.own_test.as<uint16_t>(), c->copy, &wide)) return rc;
+      if (!wide) { if (int rc = stager_upload_narrow(c->stager.get(), (const int32_t*)ref, count, sl.own_ref.as<uint16_t>(), c->copy, &wide)) return rc; }
       if (wide) ++c->n_wide_slabs;
     } else wide = true;                  // (pinned int32: the DMA engine reads it in place -- no host pass to narrow in)
     if (!wide) return cohort_submit(c, sl.own_test, sl.own_ref, n_samples, phi, expected, mixture, c->copy, ticket, 16, d_mix);
@@ -1041,7 +1017,7 @@ static int cohort_collect(ed_cohort* c, int64_t ticket, int64_t sample0, int64_t
   if (path_out && E > 0) {
     if (int rc = ensure_path(b)) return rc;
     if (layout == 1) {
-      if (!sl.path_cols) HIP_TRY(hipMalloc((void**)&sl.path_cols, (size_t)E * c->slab));
+      if (!sl.path_cols) HIP_TRY(sl.path_cols.alloc((size_t)E * c->slab));
       hipLaunchKernelGGL(k_rows_to_cols<uint8_t>, dim3((unsigned)((E + 63) / 64), (unsigned)((n + 63) / 64)), dim3(256), 0, b->stream, (const uint8_t*)b->d_path, E, n,
                          sl.path_cols);
       HIP_TRY(hipGetLastError());
@@ -1083,26 +1059,18 @@ static int cohort_run_host_slabs(ed_cohort* c, const void* test, const void* ref
     if (started) return ED_OK;
     if (int rc = cohort_start(c)) return rc;
     HIP_TRY(hipSetDevice(c->plan->device));
-    if (!c->copy) HIP_TRY(ed_stream_create(&c->copy, c->own_queues, c->plan->device));
+    if (!c->copy) HIP_TRY(ed_stream_create(c->copy, c->own_queues, c->plan->device));
     // given parameters: the whole vectors go to the device once (a pageable per-slab copy on the main stream would make the
     // host wait for that stream every time); the slabs then take their windows device to device
     if (phi) {
-      if (c->par_cap < S_total) {
-        if (c->d_par) { HIP_TRY(hipFree(c->d_par)); c->d_par = nullptr; c->par_cap = 0; }
-        HIP_TRY(hipMalloc((void**)&c->d_par, (size_t)S_total * 16));
-        c->par_cap = S_total;
-      }
+      HIP_TRY(c->d_par.reserve((size_t)S_total * 16));
       HIP_TRY(hipMemcpyAsync(c->d_par, phi, (size_t)S_total * 8, hipMemcpyHostToDevice, c->copy));
       HIP_TRY(hipMemcpyAsync(c->d_par + S_total, expected, (size_t)S_total * 8, hipMemcpyHostToDevice, c->copy));
       HIP_TRY(hipStreamSynchronize(c->copy));
     }
     // per-sample mixtures: the same way, complete on the device before any slab's constants kernel, on whichever stream that runs
     if (mix_host) {
-      if (c->mixv_cap < S_total) {
-        if (c->d_mixv) { HIP_TRY(hipFree(c->d_mixv)); c->d_mixv = nullptr; c->mixv_cap = 0; }
-        HIP_TRY(hipMalloc((void**)&c->d_mixv, (size_t)S_total * 8));
-        c->mixv_cap = S_total;
-      }
+      HIP_TRY(c->d_mixv.reserve((size_t)S_total * 8));
       HIP_TRY(hipMemcpyAsync(c->d_mixv, mix_host, (size_t)S_total * 8, hipMemcpyHostToDevice, c->copy));
       HIP_TRY(hipStreamSynchronize(c->copy));
     }
@@ -1276,27 +1244,26 @@ try {
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (int rc = ed_plan_create(&plan, dev, E, 1, off.data(), st.data(), en.data(), 1e-4, 5e4)) return rc;
-  struct Cleanup {
-    ed_plan* plan; ed_batch* b = nullptr; ed_batch* odd = nullptr; ed_stager* g = nullptr; hipStream_t s = nullptr;
-    DevBuf t, r, raw, phi, ex;
-    ~Cleanup() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } if (g) stager_free(g); if (b) ed_batch_destroy(b); if (odd) ed_batch_destroy(odd); ed_plan_destroy(plan); }
-  } k{plan};
-  HIP_TRY(ed_stream_create(&k.s, false, dev));
-  if (int rc = stager_make(&k.g, dev, (size_t)64 << 20)) return rc;
+  struct Work {      // (members go in reverse order: the feed first, then the batches, the plan, the buffers)
+    DevBuf<void> t, r, raw, phi, ex;
+    std::unique_ptr<ed_plan> plan; std::unique_ptr<ed_batch> odd, b; HostFeed f;
+  } k;
+  k.plan.reset(plan);
+  if (int rc = k.f.open(dev)) return rc;
   HIP_TRY(k.t.alloc((size_t)E * slab * 4)); HIP_TRY(k.r.alloc((size_t)E * slab * 4));
   HIP_TRY(k.raw.alloc((size_t)E * slab * 4));
   HIP_TRY(k.phi.alloc((size_t)slab * 8)); HIP_TRY(k.ex.alloc((size_t)slab * 8));
   for (int64_t s0 = 0; s0 < n_samples; s0 += slab) {
     const int64_t n = std::min(slab, n_samples - s0);
-    ed_batch*& b = (n == slab) ? k.b : k.odd;
-    if (!b) { if (int rc = ed_batch_create(&b, plan, n)) return rc; b->fit_mode = fit_mode; }
+    std::unique_ptr<ed_batch>& b = (n == slab) ? k.b : k.odd;
+    if (!b) { if (int rc = batch_make(b, plan, n)) return rc; b->fit_mode = fit_mode; }
     const size_t off_b = (layout == 1) ? (size_t)s0 * E * wire : (size_t)s0 * wire;
-    if (int rc = upload_counts(k.g, k.s, (const char*)test + off_b, E, n, layout, wire, n_samples, k.raw.p, k.t.as<int32_t>())) return rc;
-    if (int rc = upload_counts(k.g, k.s, (const char*)ref + off_b, E, n, layout, wire, n_samples, k.raw.p, k.r.as<int32_t>())) return rc;
-    if (int rc = ed_batch_fit(b, k.t.as<int32_t>(), k.r.as<int32_t>(), k.phi.as<double>(), k.ex.as<double>(), k.s)) return rc;
-    if (int rc = ed_d2h(phi_out + s0, k.phi.p, (size_t)n * 8, k.s)) return rc;
-    if (int rc = ed_d2h(expected_out + s0, k.ex.p, (size_t)n * 8, k.s)) return rc;
-    if (converged_out) { if (int rc = ed_d2h(converged_out + s0, b->fitw->done, (size_t)n * 4, k.s)) return rc; }
+    if (int rc = upload_counts(k.f.g.get(), k.f.s, (const char*)test + off_b, E, n, layout, wire, n_samples, k.raw.get(), k.t.as<int32_t>())) return rc;
+    if (int rc = upload_counts(k.f.g.get(), k.f.s, (const char*)ref + off_b, E, n, layout, wire, n_samples, k.raw.get(), k.r.as<int32_t>())) return rc;
+    if (int rc = ed_batch_fit(b.get(), k.t.as<int32_t>(), k.r.as<int32_t>(), k.phi.as<double>(), k.ex.as<double>(), k.f.s)) return rc;
+    if (int rc = ed_d2h(phi_out + s0, k.phi.get(), (size_t)n * 8, k.f.s)) return rc;
+    if (int rc = ed_d2h(expected_out + s0, k.ex.get(), (size_t)n * 8, k.f.s)) return rc;
+    if (converged_out) { if (int rc = ed_d2h(converged_out + s0, b->fitw->done, (size_t)n * 4, k.f.s)) return rc; }
   }
   return ED_OK;
 }
@@ -1313,17 +1280,13 @@ try {
   if (int rc = require_device()) return rc;
   int dev = 0;
   (void)hipGetDevice(&dev);
-  struct Cleanup {
-    ed_stager* g = nullptr; hipStream_t s = nullptr; DevBuf t, r, raw;
-    ~Cleanup() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } if (g) stager_free(g); }
-  } k;
-  HIP_TRY(ed_stream_create(&k.s, false, dev));
-  if (int rc = stager_make(&k.g, dev, (size_t)64 << 20)) return rc;
+  struct Work { DevBuf<void> t, r, raw; HostFeed f; } k;      // (the feed goes before the buffers)
+  if (int rc = k.f.open(dev)) return rc;
   HIP_TRY(k.t.alloc((size_t)n_bins * 4)); HIP_TRY(k.r.alloc((size_t)n_bins * n_refs * 4)); HIP_TRY(k.raw.alloc((size_t)n_bins * n_refs * 4));
-  if (int rc = stager_upload(k.g, test, 1, (size_t)n_bins * 4, (size_t)n_bins * 4, k.t.p, k.s)) return rc;
-  if (int rc = upload_counts(k.g, k.s, refs_colmajor, n_bins, n_refs, 1, 4, n_refs, k.raw.p, k.r.as<int32_t>())) return rc;
-  HIP_TRY(hipStreamSynchronize(k.s));
+  if (int rc = stager_upload(k.f.g.get(), test, 1, (size_t)n_bins * 4, (size_t)n_bins * 4, k.t.get(), k.f.s)) return rc;
+  if (int rc = upload_counts(k.f.g.get(), k.f.s, refs_colmajor, n_bins, n_refs, 1, 4, n_refs, k.raw.get(), k.r.as<int32_t>())) return rc;
+  HIP_TRY(hipStreamSynchronize(k.f.s));
   return ed_select_reference_set(k.t.as<int32_t>(), k.r.as<int32_t>(), n_bins, n_refs, bin_length, n_bins_reduced, rows, n_chosen,
-                                 n_selected_bins, k.s);
+                                 n_selected_bins, k.f.s);
 }
 ED_CATCH("ed_select_reference_set_host")

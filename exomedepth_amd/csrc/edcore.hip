@@ -37,6 +37,7 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
@@ -48,6 +49,12 @@
 #include "ed_sf_dev.hpp"
 #include "ed_fit_dev.hpp"
 #include "ed_dtab.h"
+#include "ed_own.hpp"
+
+using edown::DevBuf;
+using edown::PinBuf;
+using edown::Event;
+using edown::Stream;
 
 #define ED_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -1686,58 +1693,91 @@ struct ed_plan {
   int32_t C = 0;
   double tprob = 0, L = 0;
   std::vector<int32_t> chrom_off;
-  int32_t* d_chrom_off = nullptr;
-  double* d_lt3 = nullptr;       // [(E + C)][4][2]  per exon gap and quad lane: (lt[j][1], lt[j][2])
-  int64_t* d_tile_off = nullptr;  // [C + 1] back-pointer word offsets (16 steps per word) per chromosome
+  DevBuf<int32_t> d_chrom_off;
+  DevBuf<double> d_lt3;          // [(E + C)][4][2]  per exon gap and quad lane: (lt[j][1], lt[j][2])
+  DevBuf<int64_t> d_tile_off;    // [C + 1] back-pointer word offsets (16 steps per word) per chromosome
   int64_t n_words = 0;
   int64_t max_words = 0;
   double c0 = 0, c1 = 0;         // log(1 - t), log(t / 2)
 };
 
+struct FitWork;
+namespace { struct BinsWork; }
+
+// The lazily made buffer sets of a batch.  Each is built into a local and moved in whole (tab_setup, tab_setup_sm, bins_ctab_setup):
+// a set is there or it is not.
+struct TabSet {      // table-driven emission mode (edtab.inc; ed_batch_set_emit_mode): made on the first run in that mode
+  DevBuf<double> d_tabs;         // [S][tab_stride][3]
+  DevBuf<int4> d_tdims;          // [S + 64] (Ly, Lr, Tm1, reason) per sample (edtab.inc: tab_dims_of)
+  DevBuf<unsigned int> d_notab;  // [2][1 + S] samples without tables: their number, then the samples; the same for the tail samples (k_tab_build)
+  DevBuf<int4> d_twins;          // [S] (n1, n2, n3, tail): the LDS windows of the sample-major form, and whether the sample is a tail sample (edtab.inc)
+  DevBuf<double> d_tlg0;         // [S][3 tables][3 states][2] log Gamma of the tables' shape parameters (double-doubles): what a tail sample's series subtract
+  DevBuf<unsigned long long> d_tacc;   // [3][S] subsampled count sums (k_tab_stats)
+  DevBuf<uint2> d_cold_list;     // cells outside their sample's tables
+  DevBuf<unsigned int> d_cold_n;
+  DevBuf<int64_t> d_seg_t;       // emission segments for k_emit_tab's tile shape (seg_t)
+  bool made() const { return (bool)d_tabs; }
+};
+struct SmSet {       // emit mode 2 (sample-major form): the counts as [S][E], the likelihood matrix as [S][3][Epad]
+  DevBuf<int32_t> d_test_sm, d_ref_sm;
+  DevBuf<double> d_loglik_sm;
+  DevBuf<int2> d_blk_sm;               // per block of 64 exons: (its first exon, the end of its chromosome)
+  DevBuf<unsigned int> d_vit_queue;    // [8][2] work counters of k_viterbi_sm's persistent grid (one pair per launch group in flight; self-resetting)
+  bool made() const { return (bool)d_loglik_sm; }
+};
+struct CtabSet {     // depth-binned model, tabulated constants (edbins.inc)
+  DevBuf<double> d_ctab;         // [3][kBinsRtab][S] lbeta(a1, a2) of the depth-binned model per reference count
+  DevBuf<uint8_t> d_left_out;    // one byte per workgroup of k_emit_bins_tab: a cell was left to the per-cell kernel
+  bool made() const { return (bool)d_ctab; }
+};
+
+// Members are destroyed in reverse order of declaration, and ed_batch_destroy relies on it: the streams are declared first (they go
+// last, after every buffer and event), the fit and bins workspaces last (they go first).  DevBuf / Event / Stream members are owned;
+// raw pointers are borrowed (the plan, the caller's arrays, the cohort's epoch) and say so.
 struct ed_batch {
-  ed_plan* plan = nullptr;
+  ~ed_batch();                          // (where FitWork and BinsWork are complete)
+  ed_plan* plan = nullptr;              // borrowed: outlives the batch
   int64_t S = 0;
-  double* d_loglik = nullptr;
-  uint8_t* d_path = nullptr;
-  uint32_t* d_bp = nullptr;      // [n_words][S][4] packed back-pointers (16 steps x 2 bits per quad lane)
-  uint32_t* d_ppath = nullptr;   // [n_words][S] packed Viterbi states (16 exons x 2 bits)
-  uint8_t* d_maps = nullptr;     // [n_words][S] trace-back maps of the 16-step words
-  uint32_t* d_ent = nullptr;     // [n_words / 16 + C + 1][S] state of each word's last exon, 16 words per u32
-  uint8_t* d_last = nullptr;     // [C][S] state of each chain's last exon (end of the forward pass)
-  int32_t* d_job_off = nullptr;  // [n_jobs + 1]
-  int32_t* d_job_chrom = nullptr;  // chromosomes in job order
-  int64_t* d_seg = nullptr;        // emission segments in job order: (first workgroup, first exon, end exon) x n_jobs
+  std::vector<Stream> sides;            // side streams (groups round-robin): Viterbi overlaps the emissions of later groups
+  Stream fin;                           // asynchronous tail (below)
+  void replace_side(size_t i, Stream&& st) { sides[i] = std::move(st); }   // the cohort pipeline gives the chains a stream with a hardware queue of its own
+  DevBuf<double> d_loglik;
+  DevBuf<uint8_t> d_path;
+  DevBuf<uint32_t> d_bp;         // [n_words][S][4] packed back-pointers (16 steps x 2 bits per quad lane)
+  DevBuf<uint32_t> d_ppath;      // [n_words][S] packed Viterbi states (16 exons x 2 bits)
+  DevBuf<uint8_t> d_maps;        // [n_words][S] trace-back maps of the 16-step words
+  DevBuf<uint32_t> d_ent;        // [n_words / 16 + C + 1][S] state of each word's last exon, 16 words per u32
+  DevBuf<uint8_t> d_last;        // [C][S] state of each chain's last exon (end of the forward pass)
+  DevBuf<int32_t> d_job_off;     // [n_jobs + 1]
+  DevBuf<int32_t> d_job_chrom;   // chromosomes in job order
+  DevBuf<int64_t> d_seg;         // emission segments in job order: (first workgroup, first exon, end exon) x n_jobs
   std::vector<int64_t> seg;        // host copy (+ one closing entry holding the total workgroup count)
   int32_t n_jobs = 0;
   std::vector<std::vector<int>> jobs;   // host copy: chromosomes of each Viterbi job
   std::vector<int32_t> group_off;       // job ranges of the overlap groups (the set in use)
   std::vector<int32_t> group_off_model; // ... as the cost model cut them (Viterbi of a group under the emissions of the next)
   bool overlap_groups = true;           // false: ONE group -- all emissions, then all chains (ed_batch_set_viterbi_overlap)
-  std::vector<hipStream_t> sides;       // side streams (groups round-robin): Viterbi overlaps the emissions of later groups
-  std::vector<hipEvent_t> job_ev;       // emissions of group g are complete
-  std::vector<hipEvent_t> join_ev;      // Viterbi (+ trace-back) of group g is complete
-  hipEvent_t zero_ev = nullptr;         // the call counts have been zeroed (first side stream)
-  double* d_consts = nullptr;
-  double2* d_tab_gl = nullptr;   // [3][kEmitTab][S] (Gamma*(a1 + obs), log(a1 + obs))   (k_emit_tables)
-  double* d_tab_lg = nullptr;    // [3][kEmitTab][S] log Gamma(a1 + obs)
-  int* d_cflags = nullptr;
-  int32_t* d_counts = nullptr;
-  int64_t* d_offsets = nullptr;
-  int64_t* d_total = nullptr;
-  unsigned long long* d_nerr = nullptr;
-  ed_call* d_calls = nullptr;
-  uint8_t* d_left_out = nullptr;     // one byte per workgroup of k_emit_bins_tab: a cell was left to the per-cell kernel
-  double* d_ctab = nullptr;          // [3][kBinsRtab][S] lbeta(a1, a2) of the depth-binned model per reference count (edbins.inc)
-  ed_call_info* d_info = nullptr;    // decoration of the call table (grown on demand: hipFree would synchronise the device
-  int64_t info_cap = 0;              // and with it every other batch of a pipeline)
-  struct FitWork* fitw = nullptr;    // workspace of ed_batch_fit (allocated on first use)
-  void* binsw = nullptr;             // workspace of ed_batch_fit_bins' histogram form (BinsWork, edbins_hist.inc)
+  std::vector<Event> job_ev;            // emissions of group g are complete
+  std::vector<Event> join_ev;           // Viterbi (+ trace-back) of group g is complete
+  Event zero_ev;                        // the call counts have been zeroed (first side stream)
+  DevBuf<double> d_consts;
+  DevBuf<double2> d_tab_gl;      // [3][kEmitTab][S] (Gamma*(a1 + obs), log(a1 + obs))   (k_emit_tables)
+  DevBuf<double> d_tab_lg;       // [3][kEmitTab][S] log Gamma(a1 + obs)
+  DevBuf<int> d_cflags;
+  DevBuf<int32_t> d_counts;
+  DevBuf<int64_t> d_offsets;
+  DevBuf<int64_t> d_total;
+  DevBuf<unsigned long long> d_nerr;
+  DevBuf<ed_call> d_calls;       // the call table, grow-only (ed_batch_n_calls regrows it when a run needs more records)
+  int64_t calls_cap() const { return (int64_t)(d_calls.bytes() / sizeof(ed_call)); }
+  CtabSet ctab;
+  DevBuf<ed_call_info> d_info;   // decoration of the call table, grow-only (hipFree would synchronise the device and with it
+                                 // every other batch of a pipeline)
   int bins_form = 0;                 // form the last ed_batch_fit_bins took (ed_batch_fit_bins_form)
   int64_t bins_unconverged = 0;      // samples the last depth-binned fit left short of its tolerance (ed_batch_fit_bins_n_unconverged)
   int bins_pieces = 1;               // launches the depth-binned emission kernel is cut into (the cohort pipeline sets it)
-  int64_t calls_cap = 0;
-  hipStream_t stream = nullptr;         // where the results of the last run become available: the caller's stream, or `fin`
-  hipStream_t fit_stream = nullptr;     // stream of the last ed_batch_fit (its own timing events only)
+  hipStream_t stream = nullptr;         // borrowed: where the results of the last run become available: the caller's stream, or `fin`
+  hipStream_t fit_stream = nullptr;     // borrowed: stream of the last ed_batch_fit (its own timing events only)
   // Asynchronous tail (ed_batch_set_async_tail): the caller's stream carries the emissions only; the Viterbi groups run on
   // the side streams as before, and what follows them (call counts -> scan -> call records) runs on `fin` instead of
   // being joined back into the caller's stream.  `done_ev` marks the end of the run; the next ed_batch_run on this batch
@@ -1746,6 +1786,7 @@ struct ed_batch {
   // Emission launch cut in two (single-group mode only): the first `split_frac` of the workgroups, an event, the rest.  The
   // cohort pipeline (edcohort.inc) makes the NEXT slab's dispersion fit wait for that event, so that the fit is issued --
   // in stream order, whatever the host's timing -- while this slab's emissions are under way.
+  // borrowed from the caller (device arrays of the cohort pipeline or of the last run; never freed here): src_*, prepared_*, d_mix, last_*
   const double* src_phi = nullptr;      // cohort pipeline, given parameters: k_sample_consts of the next run / prepare reads (phi, expected) from
   const double* src_exp = nullptr;      // here and writes the copies the run is handed (the slot's arrays); cleared when consumed
   bool prepared_zeroed = false;         // ... batch_prepare also zeroed the run's counters (the cohort says when that is safe)
@@ -1756,13 +1797,12 @@ struct ed_batch {
   const double* prepared_mix_s = nullptr;
   const double* d_mix = nullptr;        // ed_batch_set_mixture: DEVICE double [S], one mixture per sample (NULL: the runs' scalar)
   double split_frac = 0.0;
-  hipEvent_t split_ev = nullptr;
+  Event split_ev;
   bool split_recorded = false;          // the last run recorded split_ev
   bool own_queues = false;              // streams of this batch are created with a (full) CU mask: a hardware queue each
   bool async_tail = false;
   bool last_run_async = false;          // the last run left its tail on `fin` (done_ev marks its end)
-  hipStream_t fin = nullptr;
-  hipEvent_t done_ev = nullptr, fork_ev = nullptr;
+  Event done_ev, fork_ev;
   int last_layout = 0;                  // counts_layout of the last run's inputs
   int counts_bits = 32;                 // 32: int32 counts; 16: uint16 (sample-major table mode only: ed_batch_set_counts_bits)
   int last_cb = 4;                      // bytes per count of the last run's inputs
@@ -1779,7 +1819,6 @@ struct ed_batch {
   bool keep_loglik = true;   // fused mode only: also write the [E][3][S] likelihood matrix (the S4 `likelihood` slot)
   int fit_hist = 1;          // ed_batch_fit: 1 = iterate on count histograms (one pass over the counts), geometry picked from
                              // the data; 8 / 4 / 2 = that geometry (samples per workgroup of k_fit_hist); 0 = per cell
-  // table-driven emission mode (edtab.inc; ed_batch_set_emit_mode): buffers allocated on the first run in that mode
   int counts_layout = 0;         // 0: count matrices [E][S] (sample-minor); 1: [S][E] (sample-major, R's column-major E x S matrix) --
                                  // ed_batch_set_counts_layout; layout 1 serves the histogram fit and emit mode 2
   int emit_mode = 0;             // 0: strict (GSL's arithmetic operation for operation), 1: log-gamma difference tables
@@ -1787,39 +1826,28 @@ struct ed_batch {
   double tab_reach = 8.0;        // a table covers this multiple of the sample's mean count (+ 64)
   int tab_tails = 1;             // emit mode 2: samples whose counts outgrow the LDS windows are served by Stirling's series beyond them (ed_batch_set_emit_tails)
   int64_t tab_stride = 0;        // entries between the tables of consecutive samples = 2 (capY + capR)
-  double* d_tabs = nullptr;      // [S][tab_stride][3]
-  int4* d_tdims = nullptr;       // [S + 64] (Ly, Lr, Tm1, reason) per sample (edtab.inc: tab_dims_of)
-  unsigned int* d_notab = nullptr;   // [2][1 + S] samples without tables: their number, then the samples; the same for the tail samples (k_tab_build)
-  int4* d_twins = nullptr;           // [S] (n1, n2, n3, tail): the LDS windows of the sample-major form, and whether the sample is a tail sample (edtab.inc)
-  double* d_tlg0 = nullptr;          // [S][3 tables][3 states][2] log Gamma of the tables' shape parameters (double-doubles): what a tail sample's series subtract
-  unsigned long long* d_tacc = nullptr;   // [3][S] subsampled count sums (k_tab_stats)
-  uint2* d_cold_list = nullptr;  // cells outside their sample's tables
-  unsigned int* d_cold_n = nullptr;
+  TabSet tab;
   unsigned int cold_cap = 0;
   std::vector<int64_t> seg_t;    // emission segments for k_emit_tab's tile shape (as `seg`)
-  int64_t* d_seg_t = nullptr;
-  // emit mode 2 (sample-major form): the counts as [S][E], the likelihood matrix as [S][3][Epad]; the documented [E][3][S] form
-  // (d_loglik) is made from it when an accessor asks (rows_valid)
-  int32_t* d_test_sm = nullptr;
-  int32_t* d_ref_sm = nullptr;
-  double* d_loglik_sm = nullptr;
+  // emit mode 2: the documented [E][3][S] form (d_loglik) is made from the sample-major matrix when an accessor asks (rows_valid)
+  SmSet sm;
   int64_t Epad = 0;
   std::vector<int64_t> seg_sm;   // segments in blocks of 64 exons (first block, first exon, end exon), job order
-  int2* d_blk_sm = nullptr;      // per block of that numbering: (its first exon, the end of its chromosome)
-  unsigned int* d_vit_queue = nullptr;   // [8][2] work counters of k_viterbi_sm's persistent grid (one pair per launch group in flight; self-resetting)
   int vit_waves = 1024;          // waves of that grid: the SIMDs of the device (tab_setup_sm)
   int64_t nblk_sm = 0;
   bool rows_valid = true;
   int fit_mode = 0;          // ed_batch_fit: 0 = maximum likelihood (Newton); 1 = aod::betabin's procedure (Nelder-Mead from the
                              // glm start, optim()'s defaults) on the same histograms -- ed_batch_set_fit_mode
   bool timing = false;
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t epoch = nullptr;            // (cohort pipeline, option timing) a completed event of the owner: the emission launches' start / end times are kept relative to it
-  std::vector<float>* emit_iv = nullptr; // ... appended here as (start_ms, end_ms) when a run's times are folded (ed_cohort_emission_intervals)
+  Event ev[7];
+  hipEvent_t epoch = nullptr;            // borrowed (cohort pipeline, option timing): a completed event of the owner: the emission launches' start / end times are kept relative to it
+  std::vector<float>* emit_iv = nullptr; // borrowed: ... appended here as (start_ms, end_ms) when a run's times are folded (ed_cohort_emission_intervals)
   bool have_run_times = false, have_fit_time = false;
   double stage_total[5] = {0, 0, 0, 0, 0};   // sums of the stage times of all timed runs / fits since timing was enabled
   float last_ms[5] = {0, 0, 0, 0, 0};        // stage times of the most recent folded run / fit (ed_batch_stage_ms)
   int64_t n_runs_timed = 0, n_fits_timed = 0;
+  std::unique_ptr<FitWork> fitw;     // workspace of ed_batch_fit (made on first use)
+  std::unique_ptr<BinsWork> binsw;   // workspace of ed_batch_fit_bins' histogram form (edbins_hist.inc)
 };
 
 // log-transition table of one chain: for padded positions pos[0..n-1], gaps i=1..n-1
@@ -1911,30 +1939,19 @@ static int ed_d2h(void* dst, const void* src, size_t bytes, hipStream_t st)
   return ED_OK;
 }
 
-namespace {
-// RAII device buffer for the host-buffer entry points
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  template <class T> T* as() { return (T*)p; }
-};
-}  // namespace
-
 ED_EXPORT int ed_eval_sf(int which, int64_t n, const double* x, const double* y, double* out)
 try {
   if (n < 0 || !x || !out) return ed_fail(ED_ERR_INVALID, "ed_eval_sf: bad arguments");
   if (int rc = require_device()) return rc;
   if (n == 0) return ED_OK;
-  DevBuf dx, dy, dout;
+  DevBuf<double> dx, dy, dout;
   HIP_TRY(dx.alloc(n * 8)); HIP_TRY(dy.alloc(n * 8)); HIP_TRY(dout.alloc(n * 8));
-  HIP_TRY(hipMemcpy(dx.p, x, n * 8, hipMemcpyHostToDevice));
-  if (y) HIP_TRY(hipMemcpy(dy.p, y, n * 8, hipMemcpyHostToDevice));
-  else HIP_TRY(hipMemset(dy.p, 0, n * 8));
-  hipLaunchKernelGGL(k_eval_sf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, which, n, dx.as<double>(),
-                     dy.as<double>(), dout.as<double>());
+  HIP_TRY(hipMemcpy(dx, x, n * 8, hipMemcpyHostToDevice));
+  if (y) HIP_TRY(hipMemcpy(dy, y, n * 8, hipMemcpyHostToDevice));
+  else HIP_TRY(hipMemset(dy, 0, n * 8));
+  hipLaunchKernelGGL(k_eval_sf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, which, n, dx.get(), dy.get(), dout.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
   return ED_OK;
 }
 ED_CATCH("ed_eval_sf")
@@ -1955,19 +1972,18 @@ try {
   *needed = 0;
   if (cap > 0) buf[0] = 0;
   if (n == 0) return ED_OK;
-  DevBuf dphi, dexp, dtot, dobs, dcodes;
+  DevBuf<double> dphi, dexp; DevBuf<int32_t> dtot, dobs; DevBuf<uint16_t> dcodes;
   HIP_TRY(dphi.alloc(n * 8)); HIP_TRY(dexp.alloc(n * 8)); HIP_TRY(dtot.alloc(n * 4)); HIP_TRY(dobs.alloc(n * 4));
   HIP_TRY(dcodes.alloc((size_t)n * 12));
-  HIP_TRY(hipMemcpy(dphi.p, phi, n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dexp.p, expected, n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dtot.p, total, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dobs.p, observed, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dphi, phi, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dexp, expected, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dtot, total, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dobs, observed, n * 4, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_emit_rows_sites, dim3((unsigned)((n + kEmitBlock - 1) / kEmitBlock)), dim3(kEmitBlock), 0, 0,
-                     dphi.as<double>(), dexp.as<double>(), dtot.as<int32_t>(), dobs.as<int32_t>(), n, mixture,
-                     dcodes.as<uint16_t>());
+                     dphi.get(), dexp.get(), dtot.get(), dobs.get(), n, mixture, dcodes.get());
   HIP_TRY(hipGetLastError());
   std::vector<uint16_t> codes((size_t)n * 6);
-  HIP_TRY(hipMemcpy(codes.data(), dcodes.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(codes.data(), dcodes, (size_t)n * 12, hipMemcpyDeviceToHost));
   size_t len = 0;
   auto emit = [&](const char* file, int line, const char* reason) {
     char tmp[160];
@@ -2014,7 +2030,7 @@ try {
   HIP_TRY(hipSetDevice(device));
   ed_plan* p = new (std::nothrow) ed_plan;
   if (!p) return ed_fail(ED_ERR_NOMEM, "out of host memory");
-  struct Guard { ed_plan* p; ~Guard() { if (p) ed_plan_destroy(p); } } guard{p};   // released on success only
+  std::unique_ptr<ed_plan> guard(p);   // released on success only
   p->device = device; p->E = n_exons; p->C = n_chrom; p->tprob = transition_probability; p->L = expected_cnv_length;
   p->chrom_off.assign(chrom_off, chrom_off + n_chrom + 1);
   // transitions <- matrix(c(1-t, t/2, t/2, .5,.5,0, .5,0,.5), byrow=TRUE)  (R/class_definition.R:343-347),
@@ -2081,26 +2097,21 @@ try {
   if (out_of_range)
     return ed_fail(ED_ERR_INVALID, "ed_plan_create: a padded position (first start - 2 L or last end + 2 L of a chromosome) does "
                                    "not fit a 32-bit integer (R's as.integer() would give NA, R/class_definition.R:368)");
-  hipError_t e1 = hipMalloc((void**)&p->d_lt3, lt3.size() * 8);
-  hipError_t e2 = hipMalloc((void**)&p->d_chrom_off, (size_t)(n_chrom + 1) * 4);
-  hipError_t e3 = hipMalloc((void**)&p->d_tile_off, (size_t)(n_chrom + 1) * 8);
+  hipError_t e1 = p->d_lt3.alloc(lt3.size() * 8);
+  hipError_t e2 = p->d_chrom_off.alloc((size_t)(n_chrom + 1) * 4);
+  hipError_t e3 = p->d_tile_off.alloc((size_t)(n_chrom + 1) * 8);
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
     return ed_fail(ED_ERR_NOMEM, "ed_plan_create: device allocation failed");
   HIP_TRY(hipMemcpy(p->d_lt3, lt3.data(), lt3.size() * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(p->d_chrom_off, chrom_off, (size_t)(n_chrom + 1) * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(p->d_tile_off, tile_off.data(), (size_t)(n_chrom + 1) * 8, hipMemcpyHostToDevice));
-  guard.p = nullptr;
-  *plan = p;
+  *plan = guard.release();
   return ED_OK;
 }
 ED_CATCH("ed_plan_create")
 
 ED_EXPORT void ed_plan_destroy(ed_plan* p)
 {
-  if (!p) return;
-  if (p->d_lt3) (void)hipFree(p->d_lt3);
-  if (p->d_tile_off) (void)hipFree(p->d_tile_off);
-  if (p->d_chrom_off) (void)hipFree(p->d_chrom_off);
   delete p;
 }
 
@@ -2111,19 +2122,22 @@ ED_EXPORT int64_t ed_plan_n_exons(const ed_plan* p) { return p ? p->E : 0; }
 // of the pipeline's streams can run side by side no longer depends on how many streams the process created before (DESIGN.md
 // 4.10).  Such a stream is a blocking stream (it synchronises with the legacy null stream); the library itself never uses the
 // null stream on these paths.  Falls back to an ordinary non-blocking stream if the runtime refuses the mask.
-static hipError_t ed_stream_create(hipStream_t* st, bool own_queue, int device)
+static hipError_t ed_stream_create(Stream& out, bool own_queue, int device)
 {
+  hipStream_t st = nullptr;
   if (own_queue) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) {
       const int ncu = prop.multiProcessorCount;
       std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0xffffffffu);
       if (ncu % 32) mask.back() = (1u << (ncu % 32)) - 1u;
-      if (hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()) == hipSuccess) return hipSuccess;
+      if (hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()) == hipSuccess) { out.reset(st); return hipSuccess; }
       (void)hipGetLastError();
     }
   }
-  return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+  const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  if (e == hipSuccess) out.reset(st);
+  return e;
 }
 
 // ---- batch ---------------------------------------------------------------------------------
@@ -2139,29 +2153,29 @@ try {
   HIP_TRY(hipSetDevice(plan->device));
   ed_batch* b = new (std::nothrow) ed_batch;
   if (!b) return ed_fail(ED_ERR_NOMEM, "out of host memory");
-  struct Guard { ed_batch* b; ~Guard() { if (b) ed_batch_destroy(b); } } guard{b};   // released on success only
+  std::unique_ptr<ed_batch> guard(b);   // released on success only
   b->plan = plan; b->S = n_samples;
   const int64_t E = plan->E, S = n_samples, C = plan->C;
   // capacity of the call table: generous for real data (a few hundred calls per sample); a run that needs more
   // gets a larger table from ed_batch_n_calls (the fill kernel is run again).
-  b->calls_cap = std::min<int64_t>(std::max<int64_t>(1 << 20, 512 * S), std::max<int64_t>(E * S / 2, 1));
+  const int64_t calls_cap = std::min<int64_t>(std::max<int64_t>(1 << 20, 512 * S), std::max<int64_t>(E * S / 2, 1));
   bool ok = true;
-  auto A = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes ? bytes : 1) != hipSuccess) ok = false; };
-  A((void**)&b->d_path, (size_t)E * S);
-  A((void**)&b->d_bp, (size_t)std::max<int64_t>(plan->n_words, 1) * S * 4 * 4);
-  A((void**)&b->d_ppath, (size_t)std::max<int64_t>(plan->n_words, 1) * S * 4);
-  A((void**)&b->d_maps, (size_t)std::max<int64_t>(plan->n_words, 1) * S);
-  A((void**)&b->d_ent, (size_t)(plan->n_words / 16 + C + 1) * S * 4);
-  A((void**)&b->d_last, (size_t)std::max<int64_t>(C, 1) * S);
-  A((void**)&b->d_consts, (size_t)(9 * S + 64) * 8);    // + 64: k_emit_batch's row resources reach one sample block past the last row
-  A((void**)&b->d_tab_gl, (size_t)3 * kEmitTab * S * 16);
-  A((void**)&b->d_tab_lg, (size_t)3 * kEmitTab * S * 8);
-  A((void**)&b->d_cflags, (size_t)(3 * S + 64) * 4);
-  A((void**)&b->d_counts, (size_t)S * std::max<int64_t>(C, 1) * 4);
-  A((void**)&b->d_offsets, (size_t)S * std::max<int64_t>(C, 1) * 8);
-  A((void**)&b->d_total, 8);
-  A((void**)&b->d_nerr, 64);   // [0..7] GSL error events, [8..11] "cold tasks were left out" flag of k_emit_batch, [16..39] table-mode counters (k_tab_cold)
-  A((void**)&b->d_calls, (size_t)b->calls_cap * sizeof(ed_call));
+  auto A = [&](auto& buf, size_t bytes) { if (ok && buf.alloc(bytes) != hipSuccess) ok = false; };
+  A(b->d_path, (size_t)E * S);
+  A(b->d_bp, (size_t)std::max<int64_t>(plan->n_words, 1) * S * 4 * 4);
+  A(b->d_ppath, (size_t)std::max<int64_t>(plan->n_words, 1) * S * 4);
+  A(b->d_maps, (size_t)std::max<int64_t>(plan->n_words, 1) * S);
+  A(b->d_ent, (size_t)(plan->n_words / 16 + C + 1) * S * 4);
+  A(b->d_last, (size_t)std::max<int64_t>(C, 1) * S);
+  A(b->d_consts, (size_t)(9 * S + 64) * 8);    // + 64: k_emit_batch's row resources reach one sample block past the last row
+  A(b->d_tab_gl, (size_t)3 * kEmitTab * S * 16);
+  A(b->d_tab_lg, (size_t)3 * kEmitTab * S * 8);
+  A(b->d_cflags, (size_t)(3 * S + 64) * 4);
+  A(b->d_counts, (size_t)S * std::max<int64_t>(C, 1) * 4);
+  A(b->d_offsets, (size_t)S * std::max<int64_t>(C, 1) * 8);
+  A(b->d_total, 8);
+  A(b->d_nerr, 64);   // [0..7] GSL error events, [8..11] "cold tasks were left out" flag of k_emit_batch, [16..39] table-mode counters (k_tab_cold)
+  A(b->d_calls, (size_t)calls_cap * sizeof(ed_call));
   if (!ok)
     return ed_fail(ED_ERR_NOMEM, "ed_batch_create: device allocation failed (E=%lld S=%lld)", (long long)E, (long long)S);
   {
@@ -2250,14 +2264,14 @@ try {
     b->jobs = jobs;
     const size_t n_groups = std::max<size_t>(b->group_off.size() - 1, 1);
     b->sides.resize(std::min<size_t>(n_groups, kSideStreams));
-    for (auto& sd : b->sides) HIP_TRY(ed_stream_create(&sd, false, plan->device));
+    for (auto& sd : b->sides) HIP_TRY(ed_stream_create(sd, false, plan->device));
     b->job_ev.resize(n_groups);
-    for (auto& e : b->job_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : b->job_ev) HIP_TRY(e.create(hipEventDisableTiming));
     b->join_ev.resize(n_groups);
-    for (auto& e : b->join_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&b->zero_ev, hipEventDisableTiming));
-    HIP_TRY(hipMalloc((void**)&b->d_job_off, joff.size() * 4));
-    HIP_TRY(hipMalloc((void**)&b->d_job_chrom, std::max<size_t>(jchr.size(), 1) * 4));
+    for (auto& e : b->join_ev) HIP_TRY(e.create(hipEventDisableTiming));
+    HIP_TRY(b->zero_ev.create(hipEventDisableTiming));
+    HIP_TRY(b->d_job_off.alloc(joff.size() * 4));
+    HIP_TRY(b->d_job_chrom.alloc(std::max<size_t>(jchr.size(), 1) * 4));
     HIP_TRY(hipMemcpy(b->d_job_off, joff.data(), joff.size() * 4, hipMemcpyHostToDevice));
     if (!jchr.empty()) HIP_TRY(hipMemcpy(b->d_job_chrom, jchr.data(), jchr.size() * 4, hipMemcpyHostToDevice));
     // emission segments: one per job (= chromosome), in job order, so that a whole group is ONE launch
@@ -2272,37 +2286,17 @@ try {
       }
     }
     b->seg.push_back(blk); b->seg.push_back(0); b->seg.push_back(0);
-    HIP_TRY(hipMalloc((void**)&b->d_seg, b->seg.size() * 8));
+    HIP_TRY(b->d_seg.alloc(b->seg.size() * 8));
     HIP_TRY(hipMemcpy(b->d_seg, b->seg.data(), b->seg.size() * 8, hipMemcpyHostToDevice));
   }
-  for (auto& e : b->ev) HIP_TRY(hipEventCreate(&e));
-  guard.b = nullptr;
-  *batch = b;
+  for (auto& e : b->ev) HIP_TRY(e.create());
+  *batch = guard.release();
   return ED_OK;
 }
 ED_CATCH("ed_batch_create")
 
-static void fitwork_free(struct FitWork* w);
-static void binswork_free(void* w);
-
-ED_EXPORT void ed_batch_destroy(ed_batch* b)
-{
-  if (!b) return;
-  fitwork_free(b->fitw);
-  binswork_free(b->binsw);
-  void* ptrs[] = {b->d_job_off, b->d_job_chrom, b->d_seg, b->d_maps, b->d_ent, b->d_last, b->d_ppath, b->d_loglik, b->d_path, b->d_bp, b->d_consts, b->d_tab_gl, b->d_tab_lg, b->d_cflags, b->d_counts, b->d_offsets, b->d_total, b->d_nerr, b->d_calls, b->d_info, b->d_ctab, b->d_left_out, b->d_tabs, b->d_tdims, b->d_twins, b->d_tlg0, b->d_notab, b->d_tacc, b->d_cold_list, b->d_cold_n, b->d_seg_t, b->d_test_sm, b->d_ref_sm, b->d_loglik_sm, b->d_blk_sm, b->d_vit_queue};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : b->job_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : b->join_ev) if (e) (void)hipEventDestroy(e);
-  if (b->zero_ev) (void)hipEventDestroy(b->zero_ev);
-  for (auto& sd : b->sides) if (sd) (void)hipStreamDestroy(sd);
-  if (b->fin) (void)hipStreamDestroy(b->fin);
-  if (b->split_ev) (void)hipEventDestroy(b->split_ev);
-  if (b->done_ev) (void)hipEventDestroy(b->done_ev);
-  if (b->fork_ev) (void)hipEventDestroy(b->fork_ev);
-  delete b;
-}
+// (ed_batch::~ed_batch is defined behind BinsWork, the later of the two workspace types: edbins.inc)
+ED_EXPORT void ed_batch_destroy(ed_batch* b) { delete b; }
 
 // Add the stage times of the last timed RUN to the running totals (called before its events are recorded again, and by
 // the readers).  The events belong to the previous run of this batch object; with batches used in rotation that work is a
@@ -2374,9 +2368,9 @@ try {
   if (!b) return ed_fail(ED_ERR_INVALID, "NULL batch");
   HIP_TRY(hipSetDevice(b->plan->device));
   if (on && !b->fin) {
-    HIP_TRY(ed_stream_create(&b->fin, b->own_queues, b->plan->device));
-    HIP_TRY(hipEventCreateWithFlags(&b->done_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&b->fork_ev, hipEventDisableTiming));
+    HIP_TRY(ed_stream_create(b->fin, b->own_queues, b->plan->device));
+    HIP_TRY(b->done_ev.create(hipEventDisableTiming));
+    HIP_TRY(b->fork_ev.create(hipEventDisableTiming));
   }
   b->async_tail = on != 0;
   return ED_OK;
@@ -2422,18 +2416,11 @@ constexpr int kBinsRtab = 8192;    // reference counts covered by the table of t
 }
 
 // ---- table-driven emission mode (edtab.inc): buffers, segment table, the per-run table build ----
-static void tab_release(ed_batch* b)
-{
-  void** ptrs[] = {(void**)&b->d_tabs, (void**)&b->d_tdims, (void**)&b->d_notab, (void**)&b->d_tacc, (void**)&b->d_cold_list, (void**)&b->d_cold_n, (void**)&b->d_seg_t,
-                   (void**)&b->d_twins, (void**)&b->d_tlg0};
-  for (void** q : ptrs) { if (*q) (void)hipFree(*q); *q = nullptr; }
-  (void)hipGetLastError();
-}
-
-// all of the mode's buffers or none (a half-made set must not pass for a made one on the next call: ADVICE r4)
+// A buffer set is built into a local and moved into the batch when everything about it has succeeded: a set that failed half-way is
+// released where the local goes out of scope, and the batch never holds part of one.
 static int tab_setup(ed_batch* b)
 {
-  if (b->d_tabs) return ED_OK;
+  if (b->tab.made()) return ED_OK;
   const ed_plan* p = b->plan;
   const int64_t S = b->S, E = p->E;
   b->tab_stride = 2 * ((int64_t)b->tab_capY + b->tab_capR);
@@ -2455,33 +2442,35 @@ static int tab_setup(ed_batch* b)
     blk += (nsb >= 8) ? ((neb + kTabRun - 1) / kTabRun) * (int64_t)kTabRun * 8 * ((nsb + 7) / 8) : neb * nsb;
   }
   b->seg_t.push_back(blk); b->seg_t.push_back(0); b->seg_t.push_back(0);
+  TabSet t;
   bool ok = true;
-  auto A = [&](void** q, size_t bytes) { if (ok && hipMalloc(q, bytes ? bytes : 1) != hipSuccess) { ok = false; *q = nullptr; } };
-  A((void**)&b->d_tabs, (size_t)S * b->tab_stride * 24);
-  A((void**)&b->d_tdims, (size_t)(S + 64) * 16);
-  A((void**)&b->d_notab, (size_t)2 * (S + 1) * 4);
-  A((void**)&b->d_twins, (size_t)(S + 64) * 16);
-  A((void**)&b->d_tlg0, (size_t)S * 18 * 8);
-  A((void**)&b->d_tacc, (size_t)3 * S * 8);
-  A((void**)&b->d_cold_list, (size_t)b->cold_cap * 8);
-  A((void**)&b->d_cold_n, (size_t)(kColdLists + 1) * 4);
-  A((void**)&b->d_seg_t, b->seg_t.size() * 8);
-  if (ok && hipMemset(b->d_tdims, 0, (size_t)(S + 64) * 16) != hipSuccess) ok = false;
-  if (ok && hipMemset(b->d_notab, 0, (size_t)2 * (S + 1) * 4) != hipSuccess) ok = false;
-  if (ok && hipMemset(b->d_twins, 0, (size_t)(S + 64) * 16) != hipSuccess) ok = false;
-  if (ok && hipMemcpy(b->d_seg_t, b->seg_t.data(), b->seg_t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ok = false;
+  auto A = [&](auto& buf, size_t bytes) { if (ok && buf.alloc(bytes) != hipSuccess) ok = false; };
+  A(t.d_tabs, (size_t)S * b->tab_stride * 24);
+  A(t.d_tdims, (size_t)(S + 64) * 16);
+  A(t.d_notab, (size_t)2 * (S + 1) * 4);
+  A(t.d_twins, (size_t)(S + 64) * 16);
+  A(t.d_tlg0, (size_t)S * 18 * 8);
+  A(t.d_tacc, (size_t)3 * S * 8);
+  A(t.d_cold_list, (size_t)b->cold_cap * 8);
+  A(t.d_cold_n, (size_t)(kColdLists + 1) * 4);
+  A(t.d_seg_t, b->seg_t.size() * 8);
+  if (ok && hipMemset(t.d_tdims, 0, (size_t)(S + 64) * 16) != hipSuccess) ok = false;
+  if (ok && hipMemset(t.d_notab, 0, (size_t)2 * (S + 1) * 4) != hipSuccess) ok = false;
+  if (ok && hipMemset(t.d_twins, 0, (size_t)(S + 64) * 16) != hipSuccess) ok = false;
+  if (ok && hipMemcpy(t.d_seg_t, b->seg_t.data(), b->seg_t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ok = false;
   if (ok && ed_null_stream_fence() != hipSuccess) ok = false;
   if (!ok) {
-    tab_release(b);
+    (void)hipGetLastError();
     return ed_fail(ED_ERR_NOMEM, "emit mode 1: cannot allocate the tables (%lld bytes for %lld samples)",
                    (long long)(S * b->tab_stride * 24), (long long)S);
   }
+  b->tab = std::move(t);
   return ED_OK;
 }
 
 static int tab_setup_sm(ed_batch* b)
 {
-  if (b->d_loglik_sm) return ED_OK;
+  if (b->sm.made()) return ED_OK;
   const ed_plan* p = b->plan;
   const int64_t S = b->S, E = p->E;
   b->Epad = ((E + 15) / 16) * 16 + 96;    // (k_viterbi_sm loads whole tiles up to four tiles past a chromosome's end)
@@ -2503,27 +2492,40 @@ static int tab_setup_sm(ed_batch* b)
   b->seg_sm.push_back(blk); b->seg_sm.push_back(0); b->seg_sm.push_back(0);
   if (bm.empty()) bm.push_back(make_int2(0, 0));
   b->nblk_sm = (int64_t)bm.size();
+  SmSet t;
   bool ok = true;
-  auto A = [&](void** q, size_t bytes) { if (ok && hipMalloc(q, bytes ? bytes : 1) != hipSuccess) { ok = false; *q = nullptr; } };
-  A((void**)&b->d_test_sm, (size_t)std::max<int64_t>(E, 1) * S * 4);
-  A((void**)&b->d_ref_sm, (size_t)std::max<int64_t>(E, 1) * S * 4);
-  A((void**)&b->d_blk_sm, bm.size() * 8);
-  A((void**)&b->d_vit_queue, 64);
-  A((void**)&b->d_loglik_sm, ((size_t)S * 3 * b->Epad + 512) * 8);     // (last: it is the "already set up" sentinel)
-  if (ok && hipMemset(b->d_vit_queue, 0, 64) != hipSuccess) ok = false;
+  auto A = [&](auto& buf, size_t bytes) { if (ok && buf.alloc(bytes) != hipSuccess) ok = false; };
+  A(t.d_test_sm, (size_t)std::max<int64_t>(E, 1) * S * 4);
+  A(t.d_ref_sm, (size_t)std::max<int64_t>(E, 1) * S * 4);
+  A(t.d_blk_sm, bm.size() * 8);
+  A(t.d_vit_queue, 64);
+  A(t.d_loglik_sm, ((size_t)S * 3 * b->Epad + 512) * 8);
+  if (ok && hipMemset(t.d_vit_queue, 0, 64) != hipSuccess) ok = false;
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0) b->vit_waves = prop.multiProcessorCount * 4;
   }
-  if (ok && hipMemset(b->d_loglik_sm, 0, ((size_t)S * 3 * b->Epad + 512) * 8) != hipSuccess) ok = false;
-  if (ok && hipMemcpy(b->d_blk_sm, bm.data(), bm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ok = false;
+  if (ok && hipMemset(t.d_loglik_sm, 0, ((size_t)S * 3 * b->Epad + 512) * 8) != hipSuccess) ok = false;
+  if (ok && hipMemcpy(t.d_blk_sm, bm.data(), bm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ok = false;
   if (ok && ed_null_stream_fence() != hipSuccess) ok = false;
-  if (!ok) {     // all of them or none
-    void** ptrs[] = {(void**)&b->d_test_sm, (void**)&b->d_ref_sm, (void**)&b->d_blk_sm, (void**)&b->d_vit_queue, (void**)&b->d_loglik_sm};
-    for (void** q : ptrs) { if (*q) (void)hipFree(*q); *q = nullptr; }
+  if (!ok) {
     (void)hipGetLastError();
     return ed_fail(ED_ERR_NOMEM, "emit mode 2: cannot allocate the sample-major matrices (E=%lld S=%lld)", (long long)E, (long long)S);
   }
+  b->sm = std::move(t);
+  return ED_OK;
+}
+
+// depth-binned model: the table of constants and the left-out bytes of k_emit_bins_tab (one per workgroup of the emission grid)
+static int bins_ctab_setup(ed_batch* b, size_t bytes_left_out)
+{
+  if (b->ctab.made()) return ED_OK;
+  CtabSet t;
+  if (t.d_ctab.alloc((size_t)3 * kBinsRtab * b->S * 8) != hipSuccess || t.d_left_out.alloc(bytes_left_out) != hipSuccess) {
+    (void)hipGetLastError();
+    return ed_fail(ED_ERR_NOMEM, "ed_batch_run_bins: cannot allocate the table of constants");
+  }
+  b->ctab = std::move(t);
   return ED_OK;
 }
 
@@ -2534,11 +2536,11 @@ static int ensure_loglik_rows(ed_batch* b)
   HIP_TRY(hipSetDevice(b->plan->device));      // (an accessor may be called from a thread whose current device is another one)
   const int64_t E = b->plan->E, S = b->S;
   if (!b->d_loglik) {
-    if (hipMalloc((void**)&b->d_loglik, (size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
+    if (b->d_loglik.alloc((size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
       return ed_fail(ED_ERR_NOMEM, "cannot allocate the [E][3][S] form of the likelihood matrix");
   }
   if (E > 0)
-    hipLaunchKernelGGL(k_ll_sm_to_rows, dim3((unsigned)((E + 63) / 64), (unsigned)((S + 63) / 64), 3), dim3(256), 0, b->stream, b->d_loglik_sm, E, b->Epad, S,
+    hipLaunchKernelGGL(k_ll_sm_to_rows, dim3((unsigned)((E + 63) / 64), (unsigned)((S + 63) / 64), 3), dim3(256), 0, b->stream, b->sm.d_loglik_sm, E, b->Epad, S,
                        b->d_loglik);
   HIP_TRY(hipGetLastError());
   b->rows_valid = true;
@@ -2571,16 +2573,16 @@ static int tab_build(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, h
   const int step = E >= 4096 ? 16 : 1;     // (d_tacc, d_notab[0], d_cold_n were zeroed by k_sample_consts, launched right before this on the same stream)
   const int tails = (b->emit_mode == 2 && b->tab_tails) ? 1 : 0;      // tail samples exist in the sample-major form only (edtab.inc: tab_windows)
   if (E > 0 && b->counts_layout == 1)
-    hipLaunchKernelGGL(k_tab_stats_sm, dim3((unsigned)S, 4), dim3(64), 0, st, d_test, d_ref, E, E, S, step, b->d_tacc, b->cb());
+    hipLaunchKernelGGL(k_tab_stats_sm, dim3((unsigned)S, 4), dim3(64), 0, st, d_test, d_ref, E, E, S, step, b->tab.d_tacc, b->cb());
   else if (E > 0)
     hipLaunchKernelGGL(k_tab_stats, dim3((unsigned)((S + 63) / 64), (unsigned)((E + 64 * step - 1) / (64 * step))), dim3(256), 0, st, d_test, d_ref, E, S,
-                       step, b->d_tacc);
+                       step, b->tab.d_tacc);
   if (S < 256)
-    hipLaunchKernelGGL(k_tab_build<256>, dim3((unsigned)S, 3), dim3(256), 0, st, b->d_consts, b->d_cflags, b->d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
-                       b->d_tdims, S, b->d_tabs, b->tab_stride, b->d_notab, tails, b->d_twins, b->d_tlg0);
+    hipLaunchKernelGGL(k_tab_build<256>, dim3((unsigned)S, 3), dim3(256), 0, st, b->d_consts, b->d_cflags, b->tab.d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
+                       b->tab.d_tdims, S, b->tab.d_tabs, b->tab_stride, b->tab.d_notab, tails, b->tab.d_twins, b->tab.d_tlg0);
   else
-    hipLaunchKernelGGL(k_tab_build<64>, dim3((unsigned)S, 3), dim3(64), 0, st, b->d_consts, b->d_cflags, b->d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
-                       b->d_tdims, S, b->d_tabs, b->tab_stride, b->d_notab, tails, b->d_twins, b->d_tlg0);
+    hipLaunchKernelGGL(k_tab_build<64>, dim3((unsigned)S, 3), dim3(64), 0, st, b->d_consts, b->d_cflags, b->tab.d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
+                       b->tab.d_tdims, S, b->tab.d_tabs, b->tab_stride, b->tab.d_notab, tails, b->tab.d_twins, b->tab.d_tlg0);
   HIP_TRY(hipGetLastError());
   return ED_OK;
 }
@@ -2602,8 +2604,8 @@ static int batch_prepare(ed_batch* b, const double* d_phi, const double* d_expec
   const bool from_src = b->src_phi && b->src_exp;
   hipLaunchKernelGGL(k_sample_consts, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, from_src ? b->src_phi : d_phi, from_src ? b->src_exp : d_expected, mixture, S,
                      b->d_consts, b->d_cflags,
-                     zero_counters ? b->d_nerr : (unsigned long long*)nullptr, b->emit_mode >= 1 ? b->d_tacc : (unsigned long long*)nullptr,
-                     b->emit_mode >= 1 ? b->d_notab : (unsigned int*)nullptr, b->emit_mode >= 1 ? b->d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
+                     zero_counters ? b->d_nerr : (unsigned long long*)nullptr, b->emit_mode >= 1 ? b->tab.d_tacc : (unsigned long long*)nullptr,
+                     b->emit_mode >= 1 ? b->tab.d_notab : (unsigned int*)nullptr, b->emit_mode >= 1 ? b->tab.d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
                      from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr, b->d_mix);
   b->src_phi = b->src_exp = nullptr;
   b->prepared_zeroed = zero_counters;
@@ -2660,8 +2662,8 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
     if (tabm) { if (int rc = tab_setup(b)) return rc; }
     const bool from_src = b->src_phi && b->src_exp;
     hipLaunchKernelGGL(k_sample_consts, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, from_src ? b->src_phi : d_phi, from_src ? b->src_exp : d_expected, mixture, S,
-                       b->d_consts, b->d_cflags, b->d_nerr, tabm ? b->d_tacc : (unsigned long long*)nullptr, tabm ? b->d_notab : (unsigned int*)nullptr,
-                       tabm ? b->d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
+                       b->d_consts, b->d_cflags, b->d_nerr, tabm ? b->tab.d_tacc : (unsigned long long*)nullptr, tabm ? b->tab.d_notab : (unsigned int*)nullptr,
+                       tabm ? b->tab.d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
                        from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr, b->d_mix);
     if (tabm) { if (int rc = tab_build(b, d_test, d_ref, st)) return rc; }
     else if (!b->fused)
@@ -2672,8 +2674,8 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
   if (tabsm) { if (int rc = tab_setup_sm(b)) return rc; }
   if (tabsm && E > 0 && !cl1) {   // the counts sample-major (R's own layout; with ed_batch_set_counts_layout(batch, 1) they arrive that way)
     const dim3 tg((unsigned)((E + 63) / 64), (unsigned)((S + 63) / 64));
-    hipLaunchKernelGGL(k_tab_rows_to_cols, tg, dim3(256), 0, st, d_test, E, S, b->d_test_sm);
-    hipLaunchKernelGGL(k_tab_rows_to_cols, tg, dim3(256), 0, st, d_ref, E, S, b->d_ref_sm);
+    hipLaunchKernelGGL(k_tab_rows_to_cols, tg, dim3(256), 0, st, d_test, E, S, b->sm.d_test_sm);
+    hipLaunchKernelGGL(k_tab_rows_to_cols, tg, dim3(256), 0, st, d_ref, E, S, b->sm.d_ref_sm);
   }
   const std::vector<int64_t>& segv = tabsm ? b->seg_sm : (tabm ? b->seg_t : b->seg);
   int* const cold_flag = reinterpret_cast<int*>(b->d_nerr + 1);
@@ -2689,17 +2691,17 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
       nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(nsplit, n / 32));
       const int64_t nwg = ((S + 7) / 8) * 8 * nsplit;
       if (cl1 && cb == 2)
-        hipLaunchKernelGGL(k_emit_tab_sm<2>, dim3((unsigned)nwg), dim3(kSmBlock), 0, st, d_test, d_ref, b->d_tdims, b->d_tabs, b->tab_stride,
-                           b->d_blk_sm, b->nblk_sm, base, n, nsplit, S, E, b->Epad, b->d_loglik_sm, b->d_cold_list, b->d_cold_n, b->cold_cap, b->d_twins, b->d_tlg0,
+        hipLaunchKernelGGL(k_emit_tab_sm<2>, dim3((unsigned)nwg), dim3(kSmBlock), 0, st, d_test, d_ref, b->tab.d_tdims, b->tab.d_tabs, b->tab_stride,
+                           b->sm.d_blk_sm, b->nblk_sm, base, n, nsplit, S, E, b->Epad, b->sm.d_loglik_sm, b->tab.d_cold_list, b->tab.d_cold_n, b->cold_cap, b->tab.d_twins, b->tab.d_tlg0,
                            b->d_consts);
       else
-        hipLaunchKernelGGL(k_emit_tab_sm<4>, dim3((unsigned)nwg), dim3(kSmBlock), 0, st, cl1 ? d_test : b->d_test_sm, cl1 ? d_ref : b->d_ref_sm, b->d_tdims, b->d_tabs, b->tab_stride,
-                           b->d_blk_sm, b->nblk_sm, base, n, nsplit, S, E, b->Epad, b->d_loglik_sm, b->d_cold_list, b->d_cold_n, b->cold_cap, b->d_twins, b->d_tlg0,
+        hipLaunchKernelGGL(k_emit_tab_sm<4>, dim3((unsigned)nwg), dim3(kSmBlock), 0, st, cl1 ? d_test : b->sm.d_test_sm, cl1 ? d_ref : b->sm.d_ref_sm, b->tab.d_tdims, b->tab.d_tabs, b->tab_stride,
+                           b->sm.d_blk_sm, b->nblk_sm, base, n, nsplit, S, E, b->Epad, b->sm.d_loglik_sm, b->tab.d_cold_list, b->tab.d_cold_n, b->cold_cap, b->tab.d_twins, b->tab.d_tlg0,
                            b->d_consts);
       return;
     }
-    hipLaunchKernelGGL(k_emit_tab<kTabTw>, dim3((unsigned)n), dim3(kTabBlock), 0, st, d_test, d_ref, b->d_tdims, b->d_tabs, b->tab_stride, b->d_seg_t,
-                       b->n_jobs, base, S, (uint32_t)((S + kTabTw - 1) / kTabTw), b->d_loglik, b->d_cold_list, b->d_cold_n, b->cold_cap);
+    hipLaunchKernelGGL(k_emit_tab<kTabTw>, dim3((unsigned)n), dim3(kTabBlock), 0, st, d_test, d_ref, b->tab.d_tdims, b->tab.d_tabs, b->tab_stride, b->tab.d_seg_t,
+                       b->n_jobs, base, S, (uint32_t)((S + kTabTw - 1) / kTabTw), b->d_loglik, b->tab.d_cold_list, b->tab.d_cold_n, b->cold_cap);
   };
   if (b->timing) HIP_TRY(hipEventRecord(b->ev[1], st));
   const int64_t cells = E * S;
@@ -2708,7 +2710,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
     // emissions and Viterbi together (edfused.inc); the likelihood matrix is written only if it is kept.
     HIP_TRY(hipMemsetAsync(b->d_counts, 0, (size_t)S * std::max<int64_t>(C, 1) * 4, st));   // empty chromosomes: no calls
     if (b->keep_loglik && !b->d_loglik) {
-      if (hipMalloc((void**)&b->d_loglik, (size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
+      if (b->d_loglik.alloc((size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
         return ed_fail(ED_ERR_NOMEM, "ed_batch_run: cannot allocate the likelihood matrix (%lld bytes)", (long long)(E * 3 * S * 8));
     }
     if (cells > 0 && b->n_jobs > 0)
@@ -2719,7 +2721,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
     if (b->timing) HIP_TRY(hipEventRecord(b->ev[2], st));
   } else {
     if (!b->d_loglik && !tabsm) {
-      if (hipMalloc((void**)&b->d_loglik, (size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
+      if (b->d_loglik.alloc((size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
         return ed_fail(ED_ERR_NOMEM, "ed_batch_run: cannot allocate the likelihood matrix");
     }
     // Emissions are issued group by group (groups of whole chromosomes, longest chromosomes first); when a
@@ -2738,7 +2740,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
       // previous group's Viterbi workgroups (side stream) are dispatched into the slots freed at that launch
       // boundary instead of queueing behind this group's thousands of pending workgroups.
       const int64_t blk0 = segv[3 * j0], nblk = plain ? segv[3 * j1] - blk0 : 0;
-      if (tabm && g > 0) HIP_TRY(hipMemsetAsync(b->d_cold_n, 0, (size_t)(kColdLists + 1) * 4, st));   // (group 0: zeroed by k_sample_consts)
+      if (tabm && g > 0) HIP_TRY(hipMemsetAsync(b->tab.d_cold_n, 0, (size_t)(kColdLists + 1) * 4, st));   // (group 0: zeroed by k_sample_consts)
       const int64_t head = tabsm ? ((g > 0 && nblk > 512) ? 128 : 0) : ((g > 0 && nblk > 2 * kEmitHeadBlocks) ? kEmitHeadBlocks : 0);
       if (!plain && g == 0)   // one launch over every cell; the Viterbi groups follow it
       {
@@ -2747,19 +2749,9 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
         const double* ctab = nullptr;
         if (bins > 0 && !em.cov) {
           // depth-binned dispersion: the constants lbeta(a1, a2) per (sample, state, reference count) first, then three tasks per cell
-          if (!b->d_ctab || !b->d_left_out) {   // both or neither: a half-made pair must not pass for a made one on the next call
-            if (b->d_ctab) { (void)hipFree(b->d_ctab); b->d_ctab = nullptr; }
-            if (b->d_left_out) { (void)hipFree(b->d_left_out); b->d_left_out = nullptr; }
-            if (hipMalloc((void**)&b->d_ctab, (size_t)3 * kBinsRtab * S * 8) != hipSuccess ||
-                hipMalloc((void**)&b->d_left_out, (size_t)egrid.x * egrid.y * egrid.z) != hipSuccess) {
-              if (b->d_ctab) { (void)hipFree(b->d_ctab); b->d_ctab = nullptr; }
-              b->d_left_out = nullptr;
-              (void)hipGetLastError();
-              return ed_fail(ED_ERR_NOMEM, "ed_batch_run_bins: cannot allocate the table of constants");
-            }
-          }
+          if (int rc = bins_ctab_setup(b, (size_t)egrid.x * egrid.y * egrid.z)) return rc;
           hipLaunchKernelGGL(k_bins_ctab, dim3((unsigned)((S + 63) / 64), (unsigned)(kBinsRtab / 4)), dim3(256), 0, st, bins, d_edges, d_phi, d_expected,
-                             mixture, S, kBinsRtab, b->d_ctab, em.skip, b->d_mix);
+                             mixture, S, kBinsRtab, b->ctab.d_ctab, em.skip, b->d_mix);
           // In the cohort pipeline the launch is cut into pieces: the NEXT slab's fit consists of several kernels whose workgroups need a
           // (nearly) whole CU each, and such a workgroup only gets one at a launch boundary, where the CUs drain -- under one uncut
           // launch the 3.5-ms fit took the launch's whole 13.8 ms and then stood between two emission launches.
@@ -2769,9 +2761,9 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
             if (pn <= 0) continue;
             const dim3 pgrid((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(pn, 65535), (unsigned)((pn + 65534) / 65535));
             hipLaunchKernelGGL(k_emit_bins_tab, pgrid, dim3(kEmitBlock), 0, st, d_test, d_ref, bins, d_edges, d_phi, d_expected, mixture, E, S,
-                               b->d_ctab, kBinsRtab, b->d_loglik, b->d_left_out, em.skip, pb0, pn, b->d_mix);
+                               b->ctab.d_ctab, kBinsRtab, b->d_loglik, b->ctab.d_left_out, em.skip, pb0, pn, b->d_mix);
           }
-          ctab = b->d_ctab;
+          ctab = b->ctab.d_ctab;
         }
         {
           const int tpw = ctab ? 32 : 1;   // behind the tabulated kernel nearly every tile returns on one byte (1 / 8 / 32 on one box: 17.0 / 16.2 / 16.1 ms per slab)
@@ -2780,7 +2772,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
           hipLaunchKernelGGL(k_emit_bins, fgrid,
                              dim3(kEmitBlock), 0, st, d_test, d_ref, bins, d_edges, d_phi, em.cov ? (const double*)nullptr : d_expected, em.X,
                              em.cov ? em.K : -1, em.beta, mixture, E, S, b->d_loglik,
-                             b->d_nerr, ctab, kBinsRtab, b->d_left_out, em.skip, tpw, eblk, b->d_mix);
+                             b->d_nerr, ctab, kBinsRtab, b->ctab.d_left_out, em.skip, tpw, eblk, b->d_mix);
         }
       }
       emit_launch(head, blk0);
@@ -2798,10 +2790,10 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
       emit_launch(nblk - head - cut, blk0 + head + cut);
       if (tabm && nblk > 0) {  // the cells outside their sample's tables and the samples without tables (returns at once when there are none)
         const bool csm = cl1 || tabsm;       // counts walked sample-major ([S][E]: the caller's, or this mode's transposed copy)
-        hipLaunchKernelGGL(k_tab_cold, dim3(1024), dim3(256), 0, st, csm ? (cl1 ? d_test : b->d_test_sm) : d_test, csm ? (cl1 ? d_ref : b->d_ref_sm) : d_ref,
-                           b->d_consts, b->d_cflags, b->d_tdims, b->d_cold_list, b->d_cold_n,
-                           b->cold_cap, b->d_seg_t, j0, j1, S, tabsm ? b->d_loglik_sm : b->d_loglik, b->d_nerr, tabsm ? (int64_t)1 : 3 * S,
-                           tabsm ? b->Epad : S, tabsm ? 3 * b->Epad : (int64_t)1, csm ? (int64_t)1 : S, csm ? E : (int64_t)1, b->d_notab, b->d_nerr + 2, cl1 ? cb : 4);
+        hipLaunchKernelGGL(k_tab_cold, dim3(1024), dim3(256), 0, st, csm ? (cl1 ? d_test : b->sm.d_test_sm) : d_test, csm ? (cl1 ? d_ref : b->sm.d_ref_sm) : d_ref,
+                           b->d_consts, b->d_cflags, b->tab.d_tdims, b->tab.d_cold_list, b->tab.d_cold_n,
+                           b->cold_cap, b->tab.d_seg_t, j0, j1, S, tabsm ? b->sm.d_loglik_sm : b->d_loglik, b->d_nerr, tabsm ? (int64_t)1 : 3 * S,
+                           tabsm ? b->Epad : S, tabsm ? 3 * b->Epad : (int64_t)1, csm ? (int64_t)1 : S, csm ? E : (int64_t)1, b->tab.d_notab, b->d_nerr + 2, cl1 ? cb : 4);
       }
       else if (plain && nblk > 0)   // the out-of-domain tasks of this group, if k_emit_batch met any (returns at once otherwise)
         hipLaunchKernelGGL(k_emit_cold, dim3(512), dim3(256), 0, st, d_test, d_ref, b->d_consts, b->d_seg, j0, j1, S, b->d_loglik,
@@ -2822,8 +2814,8 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
         const unsigned n_groups = (unsigned)((S + kVitChains - 1) / kVitChains), n_items = n_groups * (unsigned)(j1 - j0);
         const unsigned n_waves = std::min<unsigned>(n_items, (unsigned)std::max(1, b->vit_waves));
         hipLaunchKernelGGL(k_viterbi_sm, dim3(n_waves), dim3(kWave), 0,
-                           side, b->d_loglik_sm, b->Epad, p->d_lt3, p->c0, p->c1, p->d_chrom_off, p->d_tile_off, S, C, b->d_bp,
-                           b->d_last, b->d_job_off, b->d_job_chrom, j0, b->d_vit_queue + 2 * (g % 8), n_groups, n_items);
+                           side, b->sm.d_loglik_sm, b->Epad, p->d_lt3, p->c0, p->c1, p->d_chrom_off, p->d_tile_off, S, C, b->d_bp,
+                           b->d_last, b->d_job_off, b->d_job_chrom, j0, b->sm.d_vit_queue + 2 * (g % 8), n_groups, n_items);
       }
       else
       hipLaunchKernelGGL(k_viterbi, dim3((unsigned)((S + kVitChains - 1) / kVitChains), (unsigned)(j1 - j0)), dim3(kWave), 0,
@@ -2849,7 +2841,7 @@ static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_r
                      b->d_offsets, b->d_total);
   if (C > 0 && cells > 0)
     hipLaunchKernelGGL(k_calls_fill, dim3((unsigned)((S + kWave - 1) / kWave), (unsigned)C), dim3(kWave, kCallSeg), 0, tail,
-                       b->d_ppath, p->d_chrom_off, p->d_tile_off, S, C, b->d_offsets, b->d_counts, b->d_calls, b->calls_cap);
+                       b->d_ppath, p->d_chrom_off, p->d_tile_off, S, C, b->d_offsets, b->d_counts, b->d_calls, b->calls_cap());
   if (b->timing) HIP_TRY(hipEventRecord(b->ev[4], tail));
   if (async) HIP_TRY(hipEventRecord(b->done_ev, tail));
   HIP_TRY(hipGetLastError());
@@ -2879,83 +2871,81 @@ ED_CATCH("ed_batch_set_mixture")
 
 // workspace of the column-wise beta-binomial fit (shared by ed_batch_fit and ed_select_reference_set)
 struct FitWork {
-  double* partial = nullptr;   // [nchunk][kFitQ][S]
-  double* eta = nullptr;
-  double* lam = nullptr;
-  int* done = nullptr;
-  int32_t* colmap = nullptr;   // [S] the columns still iterating after the third full pass, packed (k_fit_compact)
-  int* n_map = nullptr;        // ... their number
-  int* fevals = nullptr;       // fit mode 1: objective evaluations of each sample's Nelder-Mead search
-  uint32_t* hist = nullptr;    // count histograms (k_fit_hist; layout and size depend on the geometry, sized for the largest)
-  int32_t* ov_y = nullptr;     // [lists][cap][S] cells beyond the histogram range, per row group of k_fit_hist
-  int32_t* ov_r = nullptr;
-  int32_t* ovn = nullptr;      // [lists][S] overflow cells of each (row group, sample)
-  int* depth = nullptr;        // largest per-sample mean total of the columns being fitted (device; k_fit_start)
-  int* h_depth = nullptr;      // the same, copied back after every fit (pinned host memory): next call's hint, -1 = none yet
+  DevBuf<double> partial;      // [nchunk][kFitQ][S]
+  DevBuf<double> eta, lam;
+  DevBuf<int> done;
+  DevBuf<int32_t> colmap;      // [S] the columns still iterating after the third full pass, packed (k_fit_compact)
+  DevBuf<int> n_map;           // ... their number
+  DevBuf<int> fevals;          // fit mode 1: objective evaluations of each sample's Nelder-Mead search
+  struct HistSet {             // the histogram form's buffers, made on its first use (alloc_hist): all four or none
+    DevBuf<uint32_t> hist;     // count histograms (k_fit_hist; layout and size depend on the geometry, sized for the largest)
+    DevBuf<int32_t> ov_y, ov_r;   // [lists][cap][S] cells beyond the histogram range, per row group of k_fit_hist
+    DevBuf<int32_t> ovn;       // [lists][S] overflow cells of each (row group, sample)
+    bool made() const { return (bool)hist; }
+  } hs;
+  DevBuf<int> depth;           // largest per-sample mean total of the columns being fitted (device; k_fit_start)
+  PinBuf<int> h_depth;         // the same, copied back after every fit (pinned host memory): next call's hint, -1 = none yet
   int64_t cap8 = 0, cap4 = 0, cap2 = 0;   // cells per list, by geometry
   int64_t nchunk = 0, S = 0, E_max = 0;
   int alloc_hist()
   {
-    if (hist) return ED_OK;
+    if (hs.made()) return ED_OK;
     const int64_t E = E_max;   // sized for the largest fit this workspace serves
     // cells per (row group, sample) list: ~1/3 of the group's rows, and lists x cap < 65536 (the 16-bit second-level bins
     // of k_fit_hnewton count the cells of all lists of a sample)
     auto cap_of = [&](int64_t lists) { return std::min<int64_t>(65535 / lists, std::max<int64_t>(8, (E / lists) / 3 + 1)); };
     cap8 = cap_of(hg8::kHistGroups); cap4 = cap_of(hg4::kHistGroups); cap2 = cap_of(hg2::kHistGroups);
     const int64_t slots = std::max({cap8 * hg8::kHistGroups, cap4 * hg4::kHistGroups, cap2 * hg2::kHistGroups});
-    // all four or none (`hist` is what says "made"): a failed allocation must not leave the sentinel set over missing lists
-    const bool ok = hipMalloc((void**)&hist, (size_t)hg2::kHistHalves * hg2::kHistK * hg2::hist_padded(S) * 4) == hipSuccess &&
-                    hipMalloc((void**)&ov_y, (size_t)slots * S * 4) == hipSuccess && hipMalloc((void**)&ov_r, (size_t)slots * S * 4) == hipSuccess &&
-                    hipMalloc((void**)&ovn, (size_t)hg2::kHistGroups * S * 4) == hipSuccess;
+    HistSet t;
+    const bool ok = t.hist.alloc((size_t)hg2::kHistHalves * hg2::kHistK * hg2::hist_padded(S) * 4) == hipSuccess &&
+                    t.ov_y.alloc((size_t)slots * S * 4) == hipSuccess && t.ov_r.alloc((size_t)slots * S * 4) == hipSuccess &&
+                    t.ovn.alloc((size_t)hg2::kHistGroups * S * 4) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();
-      void** four[] = {(void**)&hist, (void**)&ov_y, (void**)&ov_r, (void**)&ovn};
-      for (void** q : four) { if (*q) (void)hipFree(*q); *q = nullptr; }
       return ed_fail(ED_ERR_NOMEM, "beta-binomial fit: cannot allocate the count histograms");
     }
+    hs = std::move(t);
     return ED_OK;
   }
   int alloc(int64_t E, int64_t S_)
   {
     const int rc = alloc_impl(E, S_);
-    if (rc != ED_OK) release();     // nothing half-allocated stays behind
+    if (rc != ED_OK) *this = FitWork();     // nothing half-allocated stays behind
     return rc;
   }
   int alloc_impl(int64_t E, int64_t S_)
   {
-    release();
+    *this = FitWork();
     S = S_;
     E_max = E;
     nchunk = ((E + kFitChunk - 1) / kFitChunk) * kFitSub;
-    HIP_TRY(hipMalloc((void**)&partial, (size_t)std::max<int64_t>(nchunk, 1) * kFitQ * S * 8));
+    HIP_TRY(partial.alloc((size_t)std::max<int64_t>(nchunk, 1) * kFitQ * S * 8));
     // all-ones = NaN: a chunk read without having been written by the current fit shows up instead of passing as zero
     HIP_TRY(hipMemset(partial, 0xff, (size_t)std::max<int64_t>(nchunk, 1) * kFitQ * S * 8));
-    HIP_TRY(hipMalloc((void**)&eta, (size_t)S * 8));
-    HIP_TRY(hipMalloc((void**)&lam, (size_t)S * 8));
-    HIP_TRY(hipMalloc((void**)&done, (size_t)S * 4));
-    HIP_TRY(hipMalloc((void**)&colmap, (size_t)S * 4));
-    HIP_TRY(hipMalloc((void**)&n_map, 4));
-    HIP_TRY(hipMalloc((void**)&fevals, (size_t)S * 4));
+    HIP_TRY(eta.alloc((size_t)S * 8));
+    HIP_TRY(lam.alloc((size_t)S * 8));
+    HIP_TRY(done.alloc((size_t)S * 4));
+    HIP_TRY(colmap.alloc((size_t)S * 4));
+    HIP_TRY(n_map.alloc(4));
+    HIP_TRY(fevals.alloc((size_t)S * 4));
     HIP_TRY(hipMemset(fevals, 0, (size_t)S * 4));
     HIP_TRY(ed_null_stream_fence());
-    HIP_TRY(hipMalloc((void**)&depth, 4));
-    HIP_TRY(hipHostMalloc((void**)&h_depth, 4, hipHostMallocDefault));
+    HIP_TRY(depth.alloc(4));
+    HIP_TRY(h_depth.alloc(4));
     *h_depth = -1;
     return ED_OK;
   }
-  void release()
-  {
-    void* ptrs[] = {partial, eta, lam, done, colmap, n_map, fevals, hist, ov_y, ov_r, ovn, depth};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (h_depth) (void)hipHostFree(h_depth);
-    h_depth = nullptr;
-    partial = eta = lam = nullptr; done = nullptr; colmap = nullptr; n_map = nullptr; fevals = nullptr; hist = nullptr; ov_y = ov_r = ovn = nullptr; depth = nullptr;
-  }
 };
 
-static void fitwork_free(FitWork* w)
+// the fit workspace of a batch, made on first use (whole or not at all)
+static int batch_fitwork(ed_batch* b, int64_t E, int64_t S)
 {
-  if (w) { w->release(); delete w; }
+  if (b->fitw) return ED_OK;
+  std::unique_ptr<FitWork> w(new (std::nothrow) FitWork);
+  if (!w) return ed_fail(ED_ERR_NOMEM, "out of host memory");
+  if (int rc = w->alloc(E, S)) return rc;
+  b->fitw = std::move(w);
+  return ED_OK;
 }
 
 // Fit S columns: column s has test counts test[e*trs + s*tcs] and reference counts ref[e*rrs + s], e < E.
@@ -2998,30 +2988,30 @@ static int fit_columns(FitWork& w, const int32_t* d_test, int64_t trs, int64_t t
     if (const char* poison = getenv("ED_FIT_POISON")) {     // (diagnostic) the histogram workspace starts every fit from a byte pattern: a result that depends on what
       const int byte = atoi(poison) & 0xff;                // the allocation happened to hold differs with the pattern -- ED_FIT_POISON=165, =0, =255 ...
       const int64_t slots = std::max({w.cap8 * hg8::kHistGroups, w.cap4 * hg4::kHistGroups, w.cap2 * hg2::kHistGroups});
-      HIP_TRY(hipMemsetAsync(w.hist, byte, (size_t)hg2::kHistHalves * hg2::kHistK * hg2::hist_padded(w.S) * 4, st));
-      HIP_TRY(hipMemsetAsync(w.ov_y, byte, (size_t)slots * w.S * 4, st));
-      HIP_TRY(hipMemsetAsync(w.ov_r, byte, (size_t)slots * w.S * 4, st));
-      HIP_TRY(hipMemsetAsync(w.ovn, byte, (size_t)hg2::kHistGroups * w.S * 4, st));
+      HIP_TRY(hipMemsetAsync(w.hs.hist, byte, (size_t)hg2::kHistHalves * hg2::kHistK * hg2::hist_padded(w.S) * 4, st));
+      HIP_TRY(hipMemsetAsync(w.hs.ov_y, byte, (size_t)slots * w.S * 4, st));
+      HIP_TRY(hipMemsetAsync(w.hs.ov_r, byte, (size_t)slots * w.S * 4, st));
+      HIP_TRY(hipMemsetAsync(w.hs.ovn, byte, (size_t)hg2::kHistGroups * w.S * 4, st));
     }
     // Which geometries to launch: the one asked for (tests), else the one the previous fit's depth points to, else
     // (first fit of this workspace) all three.  The kernels themselves decide which of the launched ones runs, from
     // THIS fit's depth (fit_hist_runs) -- no host round trip, and a stale hint costs time, never correctness.
-    const int hint = *(volatile int*)w.h_depth;
+    const int hint = *(volatile int*)w.h_depth.get();
     const int launched = use_hist > 1 ? fit_hist_bit(use_hist) : (hint < 0 ? 7 : fit_hist_bit(fit_hist_geometry(hint)));
     HIP_TRY(hipMemcpyAsync(w.h_depth, w.depth, 4, hipMemcpyDeviceToHost, st));
 #define ED_FIT_HIST(NS, CAP)                                                                                                       \
     if ((launched & fit_hist_bit(NS::kHistId)) && sm)                                                                          \
-      hipLaunchKernelGGL(NS::k_fit_hist_sm, dim3((unsigned)S), dim3(NS::kHsBlock), 0, st, d_test, d_ref, sm_pitch, trs, E, S, w.hist, w.ov_y, w.ov_r, \
-                         w.ovn, CAP, w.depth, launched, cb);                                                                      \
+      hipLaunchKernelGGL(NS::k_fit_hist_sm, dim3((unsigned)S), dim3(NS::kHsBlock), 0, st, d_test, d_ref, sm_pitch, trs, E, S, w.hs.hist, w.hs.ov_y, w.hs.ov_r, \
+                         w.hs.ovn, CAP, w.depth, launched, cb);                                                                      \
     else if (launched & fit_hist_bit(NS::kHistId))                                                                                 \
       hipLaunchKernelGGL(NS::k_fit_hist, dim3((unsigned)((((S + NS::kHistSamples - 1) / NS::kHistSamples * NS::kHistHalves + 7) / 8) * 8)), \
-                         dim3(NS::kHistBlock), 0, st, d_test, d_ref, rrs, E, S, w.hist, w.ov_y, w.ov_r, w.ovn, CAP, w.depth, launched);
+                         dim3(NS::kHistBlock), 0, st, d_test, d_ref, rrs, E, S, w.hs.hist, w.hs.ov_y, w.hs.ov_r, w.hs.ovn, CAP, w.depth, launched);
     ED_FIT_HIST(hg8, w.cap8) ED_FIT_HIST(hg4, w.cap4) ED_FIT_HIST(hg2, w.cap2)
 #undef ED_FIT_HIST
 #define ED_FIT_NM(NS, CAP)                                                                                                         \
     if (launched & fit_hist_bit(NS::kHistId))                                                                                 \
-      hipLaunchKernelGGL(NS::k_fit_hnm, dim3((unsigned)((S + NS::kHnS - 1) / NS::kHnS)), dim3(NS::kHnS, NS::kHnY), 0, st, w.hist, w.ov_y,     \
-                         w.ov_r, w.ovn, CAP, S, w.eta, w.lam, w.done, 2000 /* optim(control = list(maxit = 2000)) */, d_test, d_ref, cell_rs,  \
+      hipLaunchKernelGGL(NS::k_fit_hnm, dim3((unsigned)((S + NS::kHnS - 1) / NS::kHnS)), dim3(NS::kHnS, NS::kHnY), 0, st, w.hs.hist, w.hs.ov_y,     \
+                         w.hs.ov_r, w.hs.ovn, CAP, S, w.eta, w.lam, w.done, 2000 /* optim(control = list(maxit = 2000)) */, d_test, d_ref, cell_rs,  \
                          E, w.depth, launched, w.fevals, cell_cs, d_phi, d_expected, sm ? 1 : 0, cb);
     if (fit_mode == 1) {
       ED_FIT_NM(hg8, w.cap8) ED_FIT_NM(hg4, w.cap4) ED_FIT_NM(hg2, w.cap2)
@@ -3031,8 +3021,8 @@ static int fit_columns(FitWork& w, const int32_t* d_test, int64_t trs, int64_t t
 #undef ED_FIT_NM
 #define ED_FIT_NEWTON(NS, CAP)                                                                                                     \
     if (launched & fit_hist_bit(NS::kHistId))                                                                                 \
-      hipLaunchKernelGGL(NS::k_fit_hnewton, dim3((unsigned)((S + NS::kHnS - 1) / NS::kHnS)), dim3(NS::kHnS, NS::kHnY), 0, st, w.hist, w.ov_y, \
-                         w.ov_r, w.ovn, CAP, S, w.eta, w.lam, w.done, 100, 1e-9 /* iterations are cheap here: converge tightly */, \
+      hipLaunchKernelGGL(NS::k_fit_hnewton, dim3((unsigned)((S + NS::kHnS - 1) / NS::kHnS)), dim3(NS::kHnS, NS::kHnY), 0, st, w.hs.hist, w.hs.ov_y, \
+                         w.hs.ov_r, w.hs.ovn, CAP, S, w.eta, w.lam, w.done, 100, 1e-9 /* iterations are cheap here: converge tightly */, \
                          d_test, d_ref, cell_rs, E, w.depth, launched, cell_cs, d_phi, d_expected, sm ? 1 : 0, cb);
     ED_FIT_NEWTON(hg8, w.cap8) ED_FIT_NEWTON(hg4, w.cap4) ED_FIT_NEWTON(hg2, w.cap2)
 #undef ED_FIT_NEWTON
@@ -3091,11 +3081,7 @@ try {
   if (E <= 0) return ed_fail(ED_ERR_INVALID, "ed_batch_fit: no exons");
   if (by < 1) return ed_fail(ED_ERR_INVALID, "ed_batch_fit_subset: row step %lld < 1 (subset.for.speed larger than the number of exons?)", (long long)by);
   HIP_TRY(hipSetDevice(b->plan->device));
-  if (!b->fitw) {
-    b->fitw = new (std::nothrow) FitWork;
-    if (!b->fitw) return ed_fail(ED_ERR_NOMEM, "out of host memory");
-    if (int rc = b->fitw->alloc(E, S)) return rc;
-  }
+  if (int rc = batch_fitwork(b, E, S)) return rc;
   b->fit_stream = st;
   if (b->timing) { if (int rc = fold_fit_time(b)) return rc; }
   if (b->timing) HIP_TRY(hipEventRecord(b->ev[5], st));
@@ -3213,7 +3199,7 @@ ED_CATCH("ed_batch_set_counts_bits")
 ED_EXPORT int ed_batch_set_emit_tables(ed_batch* b, int32_t cap_obs, int32_t cap_ref, double reach)
 try {
   if (!b) return ed_fail(ED_ERR_INVALID, "NULL batch");
-  if (b->d_tabs) return ed_fail(ED_ERR_STATE, "ed_batch_set_emit_tables: the tables are already allocated (call before ed_batch_set_emit_mode(batch, 1))");
+  if (b->tab.d_tabs) return ed_fail(ED_ERR_STATE, "ed_batch_set_emit_tables: the tables are already allocated (call before ed_batch_set_emit_mode(batch, 1))");
   if (cap_obs < 64 || cap_ref < 64 || cap_obs > (1 << 22) || cap_ref > (1 << 22) || (cap_obs & 7) || (cap_ref & 7) || !(reach >= 1.0 && reach <= 1e6))
     return ed_fail(ED_ERR_INVALID, "ed_batch_set_emit_tables: caps are multiples of 8 in [64, 2^22], reach in [1, 1e6]");
   b->tab_capY = cap_obs; b->tab_capR = cap_ref; b->tab_reach = reach;
@@ -3241,7 +3227,7 @@ ED_EXPORT int ed_batch_keep_loglik(ed_batch* b, int keep)
 try {
   if (!b) return ed_fail(ED_ERR_INVALID, "NULL batch");
   b->keep_loglik = keep != 0;
-  if (!b->keep_loglik && b->fused && b->d_loglik) { HIP_TRY(hipFree(b->d_loglik)); b->d_loglik = nullptr; }
+  if (!b->keep_loglik && b->fused) b->d_loglik.reset();
   return ED_OK;
 }
 ED_CATCH("ed_batch_keep_loglik")
@@ -3275,17 +3261,15 @@ try {
   if (int rc = batch_ready(b)) return rc;
   if (!n_calls) return ed_fail(ED_ERR_INVALID, "NULL output");
   if (int rc = ed_d2h(n_calls, b->d_total, 8, b->stream)) return rc;
-  if (*n_calls > b->calls_cap) {
+  if (*n_calls > b->calls_cap()) {
     const ed_plan* p = b->plan;
     const int64_t cap = *n_calls + *n_calls / 8 + 1024;
-    ed_call* fresh = nullptr;
-    if (hipMalloc((void**)&fresh, (size_t)cap * sizeof(ed_call)) != hipSuccess)
+    DevBuf<ed_call> fresh;     // (made before the old table goes: a failure leaves the batch as it was)
+    if (fresh.alloc((size_t)cap * sizeof(ed_call)) != hipSuccess)
       return ed_fail(ED_ERR_NOMEM, "call table: cannot allocate %lld records", (long long)cap);
-    (void)hipFree(b->d_calls);
-    b->d_calls = fresh;
-    b->calls_cap = cap;
+    b->d_calls = std::move(fresh);
     hipLaunchKernelGGL(k_calls_fill, dim3((unsigned)((b->S + kWave - 1) / kWave), (unsigned)p->C), dim3(kWave, kCallSeg), 0, b->stream,
-                       b->d_ppath, p->d_chrom_off, p->d_tile_off, b->S, p->C, b->d_offsets, b->d_counts, b->d_calls, b->calls_cap);
+                       b->d_ppath, p->d_chrom_off, p->d_tile_off, b->S, p->C, b->d_offsets, b->d_counts, b->d_calls, b->calls_cap());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(b->stream));
   }
@@ -3324,15 +3308,13 @@ try {
   const int64_t k = std::min(n, cap);
   if (k <= 0) return ED_OK;
   if (!host_info) return ed_fail(ED_ERR_INVALID, "NULL output");
-  if (k > b->info_cap) {
-    if (b->d_info) { HIP_TRY(hipFree(b->d_info)); b->d_info = nullptr; b->info_cap = 0; }
+  if ((size_t)k * sizeof(ed_call_info) > b->d_info.bytes()) {
     const int64_t cap = std::max<int64_t>(k + k / 4, 4096);
-    if (hipMalloc((void**)&b->d_info, (size_t)cap * sizeof(ed_call_info)) != hipSuccess)
+    if (b->d_info.reserve((size_t)cap * sizeof(ed_call_info)) != hipSuccess)
       return ed_fail(ED_ERR_NOMEM, "call decoration: cannot allocate %lld records", (long long)cap);
-    b->info_cap = cap;
   }
   hipLaunchKernelGGL(k_call_info, dim3((unsigned)((k + 127) / 128)), dim3(128), 0, b->stream, b->d_calls, k,
-                     (b->keep_loglik || !b->fused) ? (b->rows_valid ? b->d_loglik : b->d_loglik_sm) : (double*)nullptr, b->d_consts, b->last_test, b->last_ref,
+                     (b->keep_loglik || !b->fused) ? (b->rows_valid ? b->d_loglik : b->sm.d_loglik_sm) : (double*)nullptr, b->d_consts, b->last_test, b->last_ref,
                      b->last_expected, b->S, b->d_info, b->last_cov_X, b->last_cov_K, b->last_cov_beta, b->rows_valid ? 3 * b->S : (int64_t)1,
                      b->rows_valid ? b->S : b->Epad, b->rows_valid ? (int64_t)1 : 3 * b->Epad, b->last_layout ? (int64_t)1 : b->S,
                      b->last_layout ? b->plan->E : (int64_t)1, b->last_cb);
@@ -3378,9 +3360,9 @@ try {
   const int64_t E = b->plan->E, S = b->S;
   *n_compared = 0; *n_mismatch = 0;
   if (E == 0) return ED_OK;
-  DevBuf dcnt, dfirst;
+  DevBuf<void> dcnt, dfirst;
   HIP_TRY(dcnt.alloc(24)); HIP_TRY(dfirst.alloc((size_t)cap * sizeof(ed_emit_mismatch)));
-  HIP_TRY(hipMemsetAsync(dcnt.p, 0, 24, b->stream));
+  HIP_TRY(hipMemsetAsync(dcnt.get(), 0, 24, b->stream));
   const int64_t rows_per_block = (int64_t)(kEmitBlock / 64) * kVerifyRun;
   const int64_t eblk = (E + rows_per_block - 1) / rows_per_block;
   hipLaunchKernelGGL(k_emit_verify, dim3((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(eblk, 65535), (unsigned)((eblk + 65534) / 65535)),
@@ -3389,11 +3371,11 @@ try {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   unsigned long long c[3] = {0, 0, 0};
-  if (int rc = ed_d2h(c, dcnt.p, 24, b->stream)) return rc;
+  if (int rc = ed_d2h(c, dcnt.get(), 24, b->stream)) return rc;
   *n_mismatch = (int64_t)c[0];
   *n_compared = (int64_t)c[1];
   const int64_t k = std::min<int64_t>((int64_t)c[2], cap);
-  if (k > 0) { if (int rc = ed_d2h(first, dfirst.p, (size_t)k * sizeof(ed_emit_mismatch), b->stream)) return rc; }
+  if (k > 0) { if (int rc = ed_d2h(first, dfirst.get(), (size_t)k * sizeof(ed_emit_mismatch), b->stream)) return rc; }
   return ED_OK;
 }
 ED_CATCH("ed_batch_verify_emissions")
@@ -3413,9 +3395,9 @@ try {
   if (max_rel) *max_rel = 0.0;
   if (max_abs) *max_abs = 0.0;
   if (E == 0) return ED_OK;
-  DevBuf dcnt, dfirst;
+  DevBuf<void> dcnt, dfirst;
   HIP_TRY(dcnt.alloc(40)); HIP_TRY(dfirst.alloc((size_t)cap * sizeof(ed_emit_mismatch)));
-  HIP_TRY(hipMemsetAsync(dcnt.p, 0, 40, b->stream));
+  HIP_TRY(hipMemsetAsync(dcnt.get(), 0, 40, b->stream));
   const int64_t rows_per_block = (int64_t)(kEmitBlock / 64) * kVerifyRun;
   const int64_t eblk = (E + rows_per_block - 1) / rows_per_block;
   hipLaunchKernelGGL(k_emit_verify_tol, dim3((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(eblk, 65535), (unsigned)((eblk + 65534) / 65535)),
@@ -3424,14 +3406,14 @@ try {
                      b->d_mix);
   HIP_TRY(hipGetLastError());
   unsigned long long c[5] = {0, 0, 0, 0, 0};
-  if (int rc = ed_d2h(c, dcnt.p, 40, b->stream)) return rc;
+  if (int rc = ed_d2h(c, dcnt.get(), 40, b->stream)) return rc;
   *n_beyond = (int64_t)c[0];
   *n_compared = (int64_t)c[1];
   double d;
   if (max_rel) { std::memcpy(&d, &c[3], 8); *max_rel = d; }
   if (max_abs) { std::memcpy(&d, &c[4], 8); *max_abs = d; }
   const int64_t k = std::min<int64_t>((int64_t)c[2], cap);
-  if (k > 0) { if (int rc = ed_d2h(first, dfirst.p, (size_t)k * sizeof(ed_emit_mismatch), b->stream)) return rc; }
+  if (k > 0) { if (int rc = ed_d2h(first, dfirst.get(), (size_t)k * sizeof(ed_emit_mismatch), b->stream)) return rc; }
   return ED_OK;
 }
 ED_CATCH("ed_batch_verify_emissions_tol")
@@ -3441,10 +3423,10 @@ ED_EXPORT int ed_batch_copy_emit_tables(ed_batch* b, int64_t sample, int32_t dim
 try {
   if (int rc = batch_ready(b)) return rc;
   if (!dims || sample < 0 || sample >= b->S) return ed_fail(ED_ERR_INVALID, "ed_batch_copy_emit_tables: bad arguments");
-  if (!b->d_tabs || b->emit_mode < 1) return ed_fail(ED_ERR_STATE, "ed_batch_copy_emit_tables: the batch does not run a table-driven emit mode");
+  if (!b->tab.d_tabs || b->emit_mode < 1) return ed_fail(ED_ERR_STATE, "ed_batch_copy_emit_tables: the batch does not run a table-driven emit mode");
   int4 d, w;
-  if (int rc = ed_d2h(&d, b->d_tdims + sample, 16, b->stream)) return rc;
-  if (int rc = ed_d2h(&w, b->d_twins + sample, 16, b->stream)) return rc;
+  if (int rc = ed_d2h(&d, b->tab.d_tdims + sample, 16, b->stream)) return rc;
+  if (int rc = ed_d2h(&w, b->tab.d_twins + sample, 16, b->stream)) return rc;
   // (a tail sample's tables are its LDS windows, back to back: the lengths reported are the BUILT ones -- obs n1, ref n2 -- and of the n1 + n2
   //  entries of the tot table's slice only the first n3 are made: ed_batch_copy_table_windows)
   if (w.w) { d.x = w.x; d.y = w.y; }
@@ -3452,7 +3434,7 @@ try {
   const int64_t n = std::min<int64_t>(2 * ((int64_t)d.x + d.y), cap_entries);
   if (n > 0) {
     if (!entries) return ed_fail(ED_ERR_INVALID, "NULL output");
-    if (int rc = ed_d2h(entries, b->d_tabs + sample * b->tab_stride * 3, (size_t)n * 24, b->stream)) return rc;
+    if (int rc = ed_d2h(entries, b->tab.d_tabs + sample * b->tab_stride * 3, (size_t)n * 24, b->stream)) return rc;
   }
   return ED_OK;
 }
@@ -3465,9 +3447,9 @@ ED_EXPORT int ed_batch_copy_table_windows(ed_batch* b, int64_t sample, int32_t o
 try {
   if (int rc = batch_ready(b)) return rc;
   if (!out || sample < 0 || sample >= b->S) return ed_fail(ED_ERR_INVALID, "ed_batch_copy_table_windows: bad arguments");
-  if (!b->d_tabs || b->emit_mode < 1) return ed_fail(ED_ERR_STATE, "ed_batch_copy_table_windows: the batch does not run a table-driven emit mode");
+  if (!b->tab.d_tabs || b->emit_mode < 1) return ed_fail(ED_ERR_STATE, "ed_batch_copy_table_windows: the batch does not run a table-driven emit mode");
   int4 w;
-  if (int rc = ed_d2h(&w, b->d_twins + sample, 16, b->stream)) return rc;
+  if (int rc = ed_d2h(&w, b->tab.d_twins + sample, 16, b->stream)) return rc;
   out[0] = w.x; out[1] = w.y; out[2] = w.z; out[3] = w.w;
   return ED_OK;
 }
@@ -3492,7 +3474,7 @@ try {
   if (int rc = batch_ready(b)) return rc;
   if (!out) return ed_fail(ED_ERR_INVALID, "NULL output");
   out[0] = out[1] = out[2] = out[3] = 0;
-  if (!b->d_cold_n || b->emit_mode < 1) return ED_OK;
+  if (!b->tab.d_cold_n || b->emit_mode < 1) return ED_OK;
   unsigned long long v[4] = {0, 0, 0, 0};
   if (int rc = ed_d2h(v, b->d_nerr + 2, 32, b->stream)) return rc;
   out[0] = (int64_t)v[0]; out[1] = (int64_t)v[3]; out[2] = (int64_t)v[1]; out[3] = (int64_t)v[2];
@@ -3515,9 +3497,9 @@ ED_EXPORT int ed_batch_copy_table_dims(ed_batch* b, int64_t sample, int32_t dims
 try {
   if (int rc = batch_ready(b)) return rc;
   if (!dims || sample < 0 || sample >= b->S) return ed_fail(ED_ERR_INVALID, "ed_batch_copy_table_dims: bad arguments");
-  if (!b->d_tabs || b->emit_mode < 1) return ed_fail(ED_ERR_STATE, "ed_batch_copy_table_dims: the batch does not run a table-driven emit mode");
+  if (!b->tab.d_tabs || b->emit_mode < 1) return ed_fail(ED_ERR_STATE, "ed_batch_copy_table_dims: the batch does not run a table-driven emit mode");
   int4 d;
-  if (int rc = ed_d2h(&d, b->d_tdims + sample, 16, b->stream)) return rc;
+  if (int rc = ed_d2h(&d, b->tab.d_tdims + sample, 16, b->stream)) return rc;
   dims[0] = d.x; dims[1] = d.y; dims[2] = d.z; dims[3] = d.w;
   return ED_OK;
 }

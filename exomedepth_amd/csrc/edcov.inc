@@ -249,17 +249,13 @@ try {
   b->fit_stream = st;
   if (b->timing) { if (int rc = fold_fit_time(b)) return rc; }
   if (b->timing) HIP_TRY(hipEventRecord(b->ev[5], st));
-  if (!b->fitw) {
-    b->fitw = new (std::nothrow) FitWork;
-    if (!b->fitw) return ed_fail(ED_ERR_NOMEM, "out of host memory");
-    if (int rc = b->fitw->alloc(E, S)) return rc;
-  }
+  if (int rc = batch_fitwork(b, E, S)) return rc;
   FitWork& w = *b->fitw;
   const int64_t nblk = (E + kFitChunk - 1) / kFitChunk, nchunk = nblk * kFitSub;
   const dim3 gcol((unsigned)((S + kWave - 1) / kWave), (unsigned)nblk), bcol(kWave, kFitSub);
   const dim3 gred((unsigned)((S + kWave - 1) / kWave)), bred(kWave, kRedY);
   const dim3 g1((unsigned)((S + 255) / 256)), b1(256);
-  DevBuf dpart, dpar, dstate;
+  DevBuf<void> dpart, dpar, dstate;
   HIP_TRY(dpart.alloc((size_t)nchunk * kCovQ * S * 8));
   HIP_TRY(dpar.alloc((size_t)kCovM * S * 8));
   HIP_TRY(dstate.alloc((size_t)(2 * kCovM + 2) * S * 8));

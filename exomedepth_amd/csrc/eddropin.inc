@@ -19,16 +19,13 @@ namespace {
 struct DropinScratch {
   std::mutex mu;
   int device = -1;
-  char* dev = nullptr;
-  size_t dev_cap = 0;
-  char* pin = nullptr;
-  size_t pin_cap = 0;
-  hipStream_t st = nullptr;
+  DevBuf<char> dev;     // both blocks grow-only
+  PinBuf<char> pin;
+  Stream st;
   void release()
   {
-    if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; }
-    if (dev) { (void)hipFree(dev); dev = nullptr; dev_cap = 0; }
-    if (pin) { (void)hipHostFree(pin); pin = nullptr; pin_cap = 0; }
+    if (st) (void)hipStreamSynchronize(st);
+    st.reset(); dev.reset(); pin.reset();
     device = -1;
   }
 };
@@ -41,19 +38,19 @@ static int dropin_reserve(DropinScratch& s, size_t dev_bytes, size_t pin_bytes)
   int cur = 0;
   HIP_TRY(hipGetDevice(&cur));
   if (s.device != cur) { s.release(); s.device = cur; }
-  if (!s.st) HIP_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-  auto grown = [](size_t need, size_t have) { return (std::max(need + need / 2, have * 2) + ((size_t)1 << 20)) & ~(((size_t)1 << 20) - 1); };
-  if (s.dev_cap < dev_bytes) {
-    if (s.dev) { HIP_TRY(hipStreamSynchronize(s.st)); HIP_TRY(hipFree(s.dev)); s.dev = nullptr; s.dev_cap = 0; }
-    const size_t cap = grown(dev_bytes, s.dev_cap);
-    HIP_TRY(hipMalloc((void**)&s.dev, cap));
-    s.dev_cap = cap;
+  if (!s.st) {
+    hipStream_t st = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    s.st.reset(st);
   }
-  if (s.pin_cap < pin_bytes) {
-    if (s.pin) { HIP_TRY(hipStreamSynchronize(s.st)); HIP_TRY(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
-    const size_t cap = grown(pin_bytes, s.pin_cap);
-    HIP_TRY(hipHostMalloc((void**)&s.pin, cap, hipHostMallocDefault));
-    s.pin_cap = cap;
+  auto grown = [](size_t need, size_t have) { return (std::max(need + need / 2, have * 2) + ((size_t)1 << 20)) & ~(((size_t)1 << 20) - 1); };
+  if (s.dev.bytes() < dev_bytes) {      // (a block in use by the stream's queued work is waited for before it goes)
+    if (s.dev) HIP_TRY(hipStreamSynchronize(s.st));
+    HIP_TRY(s.dev.reserve(grown(dev_bytes, s.dev.bytes())));
+  }
+  if (s.pin.bytes() < pin_bytes) {
+    if (s.pin) HIP_TRY(hipStreamSynchronize(s.st));
+    HIP_TRY(s.pin.reserve(grown(pin_bytes, s.pin.bytes())));
   }
   return ED_OK;
 }
@@ -450,7 +447,7 @@ try {
   const size_t o_out = rows_bytes, o_bpq = o_out + ((out_bytes + 15) & ~(size_t)15), o_wsum = o_bpq + (size_t)(nw + 2) * 16, o_maps = o_wsum + (size_t)nw * 16,
                o_ent = o_maps + (((size_t)nw + 15) & ~(size_t)15), dev_bytes = o_ent + (size_t)nw + 16;
   if (int rc = dropin_reserve(s, dev_bytes, rows_bytes + out_bytes)) return rc;
-  double* hrows = reinterpret_cast<double*>(s.pin);
+  double* hrows = reinterpret_cast<double*>(s.pin.get());
   double* hout = reinterpret_cast<double*>(s.pin + rows_bytes);
   {
     const double lt0[3] = {std::log(transitions[0]), std::log(transitions[3]), std::log(transitions[6])};     // log(trans[0]) = log T[0, j] (src/hmm.cpp:74, :79)
@@ -471,7 +468,7 @@ try {
     pool.join();
   }
   HIP_TRY(hipMemcpyAsync(s.dev, hrows, (size_t)m * 128, hipMemcpyHostToDevice, s.st));
-  hipLaunchKernelGGL(k_hmm_forward, dim3(1), dim3(kWave), 0, s.st, reinterpret_cast<const double2*>(s.dev), m, reinterpret_cast<uint32_t*>(s.dev + o_bpq));
+  hipLaunchKernelGGL(k_hmm_forward, dim3(1), dim3(kWave), 0, s.st, reinterpret_cast<const double2*>(s.dev.get()), m, reinterpret_cast<uint32_t*>(s.dev + o_bpq));
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_hmm_traceback, dim3(1), dim3(kHmmTbThreads), 0, s.st, reinterpret_cast<const uint32_t*>(s.dev + o_bpq), m,
                      reinterpret_cast<uint8_t*>(s.dev + o_maps), reinterpret_cast<uint8_t*>(s.dev + o_ent), reinterpret_cast<int4*>(s.dev + o_wsum),

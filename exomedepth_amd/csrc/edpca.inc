@@ -433,13 +433,8 @@ double g_pca_info[ED_PCA_INFO_N] = {0};
 std::vector<double> g_pca_basis;        // the last call's U_k, [S][k]
 int64_t g_pca_basis_S = 0, g_pca_basis_k = 0;
 
-struct PcaEvents {
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~PcaEvents() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
 struct PcaStage12 {
-  DevBuf rs, div, centre, flag, mask, sel, nsel, part, G;
+  DevBuf<void> rs, div, centre, flag, mask, sel, nsel, part, G;
   int64_t n = 0, Sp = 0;
 };
 
@@ -463,24 +458,24 @@ static int pca_check_args(const char* who, const void* d_counts, int64_t E, int6
 
 // stages 1 and 2 on stream st: row statistics, the selected list, G.  ev (optional): events recorded at the start, after stage 1, after stage 2.
 static int pca_stage12(const char* who, const int32_t* d_counts, int64_t E, int64_t S, const uint8_t* mask_exons, const double* sample_div, double sd_min,
-                       hipStream_t st, PcaStage12& w, hipEvent_t* ev)
+                       hipStream_t st, PcaStage12& w, const Event* ev)
 {
   HIP_TRY(w.rs.alloc((size_t)E * 8)); HIP_TRY(w.div.alloc((size_t)S * 8)); HIP_TRY(w.centre.alloc((size_t)E * 8));
   HIP_TRY(w.flag.alloc((size_t)E)); HIP_TRY(w.sel.alloc((size_t)E * 4)); HIP_TRY(w.nsel.alloc(8));
   if (mask_exons) {
     HIP_TRY(w.mask.alloc((size_t)E));
-    HIP_TRY(hipMemcpyAsync(w.mask.p, mask_exons, (size_t)E, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w.mask.get(), mask_exons, (size_t)E, hipMemcpyHostToDevice, st));
   }
   if (ev) HIP_TRY(hipEventRecord(ev[0], st));
   const unsigned row_blocks = (unsigned)((E + 3) / 4);
   hipLaunchKernelGGL(k_pca_rowsum, dim3(row_blocks), dim3(256), 0, st, d_counts, E, S, w.rs.as<double>());
-  if (sample_div) HIP_TRY(hipMemcpyAsync(w.div.p, sample_div, (size_t)S * 8, hipMemcpyHostToDevice, st));
+  if (sample_div) HIP_TRY(hipMemcpyAsync(w.div.get(), sample_div, (size_t)S * 8, hipMemcpyHostToDevice, st));
   else hipLaunchKernelGGL(k_pca_div, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, w.rs.as<double>(), S, w.div.as<double>());
   hipLaunchKernelGGL(k_pca_rowstats, dim3(row_blocks), dim3(256), 0, st, d_counts, E, S, w.div.as<double>(), mask_exons ? w.mask.as<uint8_t>() : nullptr,
                      sd_min, w.centre.as<double>(), w.flag.as<uint8_t>());
   hipLaunchKernelGGL(k_pca_compact, dim3(1), dim3(1024), 0, st, w.flag.as<uint8_t>(), E, w.sel.as<int32_t>(), w.nsel.as<int64_t>());
   HIP_TRY(hipGetLastError());
-  if (int rc = ed_d2h(&w.n, w.nsel.p, 8, st)) return rc;
+  if (int rc = ed_d2h(&w.n, w.nsel.get(), 8, st)) return rc;
   if (ev) HIP_TRY(hipEventRecord(ev[1], st));
   if (w.n < 1) return ed_fail(ED_ERR_INVALID, "%s: no exon has a standard deviation above sd_min = %g%s", who, sd_min, mask_exons ? " outside the mask" : "");
   w.Sp = (S + kPcaTile - 1) / kPcaTile * kPcaTile;
@@ -505,10 +500,10 @@ try {
   hipStream_t st = (hipStream_t)stream;
   PcaStage12 w;
   if (int rc = pca_stage12("ed_pca_gram", d_counts, E, S, mask_exons, sample_div, sd_min, st, w, nullptr)) return rc;
-  HIP_TRY(hipMemcpyAsync(G_out, w.G.p, (size_t)S * S * 8, hipMemcpyDeviceToHost, st));
-  if (centre_out) HIP_TRY(hipMemcpyAsync(centre_out, w.centre.p, (size_t)E * 8, hipMemcpyDeviceToHost, st));
-  if (div_out) HIP_TRY(hipMemcpyAsync(div_out, w.div.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-  if (selected_out) HIP_TRY(hipMemcpyAsync(selected_out, w.flag.p, (size_t)E, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(G_out, w.G.get(), (size_t)S * S * 8, hipMemcpyDeviceToHost, st));
+  if (centre_out) HIP_TRY(hipMemcpyAsync(centre_out, w.centre.get(), (size_t)E * 8, hipMemcpyDeviceToHost, st));
+  if (div_out) HIP_TRY(hipMemcpyAsync(div_out, w.div.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+  if (selected_out) HIP_TRY(hipMemcpyAsync(selected_out, w.flag.get(), (size_t)E, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (n_selected) *n_selected = w.n;
   return ED_OK;
@@ -529,21 +524,21 @@ try {
   if (!(tol > 0.0) || max_iter < 1) return ed_fail(ED_ERR_INVALID, "%s: tol = %g, max_iter = %d", who, tol, (int)max_iter);
   if (int rc = require_device()) return rc;
   hipStream_t st = (hipStream_t)stream;
-  PcaEvents pe;
-  for (auto& e : pe.ev) HIP_TRY(hipEventCreate(&e));
+  Event pe[5];
+  for (auto& e : pe) HIP_TRY(e.create());
   PcaStage12 w;
-  if (int rc = pca_stage12(who, d_counts, E, S, mask_exons, sample_div, sd_min, st, w, pe.ev)) return rc;
+  if (int rc = pca_stage12(who, d_counts, E, S, mask_exons, sample_div, sd_min, st, w, pe)) return rc;
   const int k = n_pcs;
   if (k >= w.n)
     return ed_fail(ED_ERR_INVALID, "%s: nPCs = %d must be below the number of selected exons (%lld)", who, k, (long long)w.n);
   const int b = (int)std::min<int64_t>(S, std::max(2 * k, k + 8));
   // ---- stage 3 ----
-  DevBuf Q, Z, X, Y, T, H, W, Wt, theta, res2, bad;
+  DevBuf<void> Q, Z, X, Y, T, H, W, Wt, theta, res2, bad;
   const size_t sb = (size_t)S * b * 8, bb = (size_t)b * b * 8;
   HIP_TRY(Q.alloc(sb)); HIP_TRY(Z.alloc(sb)); HIP_TRY(X.alloc(sb)); HIP_TRY(Y.alloc(sb)); HIP_TRY(T.alloc(sb));
   HIP_TRY(H.alloc(bb)); HIP_TRY(W.alloc(bb)); HIP_TRY(Wt.alloc(bb)); HIP_TRY(theta.alloc((size_t)b * 8)); HIP_TRY(res2.alloc((size_t)b * 8));
   HIP_TRY(bad.alloc(4));
-  HIP_TRY(hipMemsetAsync(bad.p, 0, 4, st));
+  HIP_TRY(hipMemsetAsync(bad.get(), 0, 4, st));
   const int two_in_lds = 2 * bb <= (size_t)128 * 1024;      // b <= 90: the rotations / the inverse next to the matrix in LDS
   const size_t small_lds = two_in_lds ? 2 * bb : bb;
   if (small_lds > 48 * 1024) {
@@ -552,7 +547,7 @@ try {
   }
   const unsigned sb_blocks = (unsigned)(((int64_t)S * b + 255) / 256);
   // Q <- orthonormal basis of the columns of A (Cholesky QR, twice): A -> T -> Q
-  auto orthonormalise = [&](DevBuf& A) -> int {
+  auto orthonormalise = [&](DevBuf<void>& A) -> int {
     double* src = A.as<double>();
     for (int pass = 0; pass < 2; ++pass) {
       double* dst = pass == 0 ? T.as<double>() : Q.as<double>();
@@ -584,9 +579,9 @@ try {
     hipLaunchKernelGGL(k_pca_colnorm2, dim3((unsigned)b), dim3(256), 0, st, T.as<double>(), S, b, res2.as<double>());
     HIP_TRY(hipGetLastError());
     // one host round trip per iteration: b + b doubles and a flag (its cost is part of the "eigenvectors" stage time)
-    HIP_TRY(hipMemcpyAsync(h_theta.data(), theta.p, (size_t)b * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_res2.data(), res2.p, (size_t)b * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_theta.data(), theta.get(), (size_t)b * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_res2.data(), res2.get(), (size_t)b * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_bad, bad.get(), 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h_bad) return ed_fail(ED_ERR_STATE, "%s: the iteration's basis lost rank after %d iterations (Cholesky pivot not positive)", who, iters);
     if (!(h_theta[0] > 0.0)) return ed_fail(ED_ERR_STATE, "%s: the Gram matrix has no positive eigenvalue (theta_1 = %g)", who, h_theta[0]);
@@ -598,15 +593,15 @@ try {
     if (iters < max_iter) if (int rc = orthonormalise(Y)) return rc;
   }
   const double gap = (k < b && h_theta[(size_t)k] > 0.0) ? h_theta[(size_t)k - 1] / h_theta[(size_t)k] : std::numeric_limits<double>::infinity();
-  HIP_TRY(hipEventRecord(pe.ev[3], st));
+  HIP_TRY(hipEventRecord(pe[3], st));
   // what ed_pca_last_info reports; after a call that did not converge: the stages that ran, [7] the time spent iterating, [8] and [9] zero
   auto save_info = [&](int last_ev) -> int {
     std::lock_guard<std::mutex> lk(g_pca_mu);
     for (auto& v : g_pca_info) v = 0.0;
     g_pca_info[0] = iters; g_pca_info[1] = rel; g_pca_info[2] = (double)w.n; g_pca_info[3] = b; g_pca_info[4] = k;
     float ms = 0.f;
-    for (int q = 0; q < last_ev; ++q) { HIP_TRY(hipEventElapsedTime(&ms, pe.ev[q], pe.ev[q + 1])); g_pca_info[5 + q] = ms; }
-    if (last_ev == 4) { HIP_TRY(hipEventElapsedTime(&ms, pe.ev[0], pe.ev[4])); g_pca_info[9] = ms; }
+    for (int q = 0; q < last_ev; ++q) { HIP_TRY(hipEventElapsedTime(&ms, pe[q], pe[q + 1])); g_pca_info[5 + q] = ms; }
+    if (last_ev == 4) { HIP_TRY(hipEventElapsedTime(&ms, pe[0], pe[4])); g_pca_info[9] = ms; }
     g_pca_info[10] = kPcaGramSlices;
     g_pca_info[11] = (double)(((w.n + kPcaChunk - 1) / kPcaChunk + kPcaGramSlices - 1) / kPcaGramSlices * kPcaChunk);
     g_pca_info[12] = gap;
@@ -616,20 +611,20 @@ try {
     return ED_OK;
   };
   if (!converged) {
-    HIP_TRY(hipEventSynchronize(pe.ev[3]));
+    HIP_TRY(hipEventSynchronize(pe[3]));
     if (int rc = save_info(3)) return rc;
     return ed_fail(ED_ERR_STATE, "%s: the subspace iteration did not converge: %d iterations, residual %.3e of theta_1 (tol %.3e), theta_k / theta_k+1 = %.6g",
                    who, iters, rel, tol, gap);
   }
   // ---- stage 4 ----
-  DevBuf emul, smul;
+  DevBuf<void> emul, smul;
   if (exon_mul) {
     HIP_TRY(emul.alloc((size_t)E * 8));
-    HIP_TRY(hipMemcpyAsync(emul.p, exon_mul, (size_t)E * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(emul.get(), exon_mul, (size_t)E * 8, hipMemcpyHostToDevice, st));
   }
   if (sample_mul) {
     HIP_TRY(smul.alloc((size_t)S * 8));
-    HIP_TRY(hipMemcpyAsync(smul.p, sample_mul, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(smul.get(), sample_mul, (size_t)S * 8, hipMemcpyHostToDevice, st));
   }
   {
     const size_t ulds = (size_t)S * k * 8;
@@ -640,9 +635,9 @@ try {
                        u_in_lds, d_out);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(pe.ev[4], st));
+  HIP_TRY(hipEventRecord(pe[4], st));
   std::vector<double> hX((size_t)S * b);
-  HIP_TRY(hipMemcpyAsync(hX.data(), X.p, sb, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(hX.data(), X.get(), sb, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (int rc = save_info(4)) return rc;
   {

@@ -642,21 +642,16 @@ k_link_copy(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
 struct RcLink {
-  char* up = nullptr;   size_t up_cap = 0, up_used = 0;       // host -> device staging (pinned)
-  char* down = nullptr; size_t down_cap = 0, down_used = 0;   // device -> host staging (pinned)
+  PinBuf<char> up;   size_t up_used = 0;       // host -> device staging (pinned)
+  PinBuf<char> down; size_t down_used = 0;     // device -> host staging (pinned)
   struct Pending { void* dst; const char* src; size_t bytes; };
   std::vector<Pending> pending;
-  void release()
-  {
-    if (up) (void)hipHostFree(up);
-    if (down) (void)hipHostFree(down);
-    up = down = nullptr; up_cap = down_cap = up_used = down_used = 0; pending.clear();
-  }
+  void release() { up.reset(); down.reset(); up_used = down_used = 0; pending.clear(); }
   int begin(size_t cap)       // start of a call: both blocks there (or not: everything then goes through hipMemcpyAsync), nothing pending
   {
     up_used = down_used = 0; pending.clear();
-    if (!up && hipHostMalloc((void**)&up, cap, hipHostMallocDefault) == hipSuccess) up_cap = cap; else if (!up) { up = nullptr; (void)hipGetLastError(); }
-    if (!down && hipHostMalloc((void**)&down, cap, hipHostMallocDefault) == hipSuccess) down_cap = cap; else if (!down) { down = nullptr; (void)hipGetLastError(); }
+    if (!up && up.alloc(cap) != hipSuccess) (void)hipGetLastError();
+    if (!down && down.alloc(cap) != hipSuccess) (void)hipGetLastError();
     return ED_OK;
   }
   static unsigned blocks_for(size_t words) { return (unsigned)std::max<size_t>(1, std::min<size_t>(256, (words + 1023) / 1024)); }
@@ -664,7 +659,7 @@ struct RcLink {
   {
     const size_t need = (bytes + 15) & ~(size_t)15;
     if (bytes == 0) return ED_OK;
-    if ((bytes & 3) || !up || up_used + need > up_cap) { HIP_TRY(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, st)); return ED_OK; }
+    if ((bytes & 3) || !up || up_used + need > up.bytes()) { HIP_TRY(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, st)); return ED_OK; }
     char* q = up + up_used; up_used += need;         // (a region is written once per call: the kernel that reads it may still be queued)
     std::memcpy(q, h_src, bytes);
     hipLaunchKernelGGL(k_link_copy, dim3(blocks_for(bytes / 4)), dim3(256), 0, st, (const uint32_t*)q, (uint32_t*)d_dst, bytes / 4);
@@ -674,7 +669,7 @@ struct RcLink {
   {
     const size_t need = (bytes + 15) & ~(size_t)15;
     if (bytes == 0) return ED_OK;
-    if ((bytes & 3) || !down || down_used + need > down_cap) { HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, st)); return ED_OK; }
+    if ((bytes & 3) || !down || down_used + need > down.bytes()) { HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, st)); return ED_OK; }
     char* q = down + down_used; down_used += need;
     hipLaunchKernelGGL(k_link_copy, dim3(blocks_for(bytes / 4)), dim3(256), 0, st, (const uint32_t*)d_src, (uint32_t*)q, bytes / 4);
     pending.push_back({h_dst, q, bytes});
@@ -694,7 +689,7 @@ struct RcLink {
 // unmaps (seen as an outlier of the phase timer).  One call at a time uses it (a mutex); ed_release_scratch() gives it back.
 struct RcScratch {
   std::mutex mu;
-  std::vector<std::pair<void*, size_t>> bufs;
+  std::vector<DevBuf<void>> bufs;     // grow-only, handed out in call order
   size_t next = 0;
   int device = -1;
   FitWork fw;
@@ -702,24 +697,17 @@ struct RcScratch {
   RcLink link;
   void release_all()
   {
-    for (auto& b : bufs) if (b.first) (void)hipFree(b.first);
     bufs.clear(); next = 0;
-    fw.release(); fw_E = fw_S = 0;
+    fw = FitWork(); fw_E = fw_S = 0;
     link.release();
   }
   hipError_t get(void** p, size_t bytes)
   {
-    if (next == bufs.size()) bufs.push_back({nullptr, 0});
-    auto& b = bufs[next++];
-    if (b.second < bytes || !b.first) {
-      if (b.first) (void)hipFree(b.first);
-      b.first = nullptr; b.second = 0;
-      const hipError_t e = hipMalloc(&b.first, bytes ? bytes : 1);
-      if (e != hipSuccess) return e;
-      b.second = bytes ? bytes : 1;
-    }
-    *p = b.first;
-    return hipSuccess;
+    if (next == bufs.size()) bufs.emplace_back();
+    DevBuf<void>& b = bufs[next++];
+    const hipError_t e = b.reserve(bytes);
+    *p = b.get();
+    return e;
   }
   int fit_work(int64_t E, int64_t S, FitWork** out)
   {
@@ -731,7 +719,7 @@ struct RcScratch {
     return ED_OK;
   }
 };
-RcScratch g_rc_scratch;
+RcScratch& g_rc_scratch = *new RcScratch;     // (never destroyed at exit: the HIP runtime may be gone by then; ed_release_scratch() gives the memory back)
 // how the last call's chunks were served (under the scratch mutex): chunks by k_rc_column, chunks left to the row-major kernels, columns with counts
 // beyond the bins, the largest number of Newton iterations of a column, columns served by the large geometry -- ed_refcohort_last_path
 int64_t g_rc_last_path[5] = {0, 0, 0, 0, 0};
@@ -1129,12 +1117,12 @@ static int refcohort_impl(const int32_t* d_counts, int64_t n_bins, int64_t n_sam
   // tests whose loop does not stop within K prefixes: the single-test entry on the matrix without the test's column (all S - 1
   // prefixes; slow, rare: it needs a cohort in which summing K samples still leaves the test above 5 % of the total)
   {
-    DevBuf dt, dr;
+    DevBuf<void> dt, dr;
     std::vector<ed_refset_row> full;
     for (int64_t t = tb; t < te; ++t) {
       const int64_t tl = t - tb;
       if (!fallback[(size_t)tl]) continue;
-      if (!dt.p) { HIP_TRY(dt.alloc((size_t)E * 4)); HIP_TRY(dr.alloc((size_t)E * (S - 1) * 4)); full.resize((size_t)(S - 1)); }
+      if (!dt.get()) { HIP_TRY(dt.alloc((size_t)E * 4)); HIP_TRY(dr.alloc((size_t)E * (S - 1) * 4)); full.resize((size_t)(S - 1)); }
       hipLaunchKernelGGL(k_rc_split_column, dim3((unsigned)((S + 255) / 256), (unsigned)std::min<int64_t>(E, 65535)), dim3(256), 0, st, d_counts, E, S, t,
                          dt.as<int32_t>(), dr.as<int32_t>());
       int32_t nc = 0;
@@ -1261,6 +1249,12 @@ try {
 }
 ED_CATCH("ed_release_scratch")
 
+ED_EXPORT void ed_live_allocations(int64_t* n, int64_t* bytes)
+{
+  if (n) *n = edown::g_live_n.load(std::memory_order_relaxed);
+  if (bytes) *bytes = edown::g_live_bytes.load(std::memory_order_relaxed);
+}
+
 // The same on host data in R's layout: counts = the n_bins x n_samples integer matrix, column-major; reference_out (optional) the
 // aggregate reference in that layout.  What the R-level wrapper ed_cohort_reference_sets (shim/edcore_shim.c) calls.
 ED_EXPORT int ed_cohort_select_reference_sets_host(const int32_t* counts_colmajor, int64_t n_bins, int64_t n_samples, const double* bin_length,
@@ -1273,20 +1267,16 @@ try {
   int dev = 0;
   (void)hipGetDevice(&dev);
   const int64_t E = n_bins, S = n_samples;
-  struct Cleanup {
-    ed_stager* g = nullptr; hipStream_t s = nullptr; DevBuf c, raw, ref;
-    ~Cleanup() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } if (g) stager_free(g); }
-  } k;
-  HIP_TRY(ed_stream_create(&k.s, false, dev));
-  if (int rc = stager_make(&k.g, dev, (size_t)64 << 20)) return rc;
+  struct Work { DevBuf<void> c, raw, ref; HostFeed f; } k;      // (the feed goes before the buffers)
+  if (int rc = k.f.open(dev)) return rc;
   HIP_TRY(k.c.alloc((size_t)E * S * 4)); HIP_TRY(k.raw.alloc((size_t)E * S * 4));
   if (reference_out_colmajor) HIP_TRY(k.ref.alloc((size_t)E * S * 4));
-  if (int rc = upload_counts(k.g, k.s, counts_colmajor, E, S, 1, 4, S, k.raw.p, k.c.as<int32_t>())) return rc;
+  if (int rc = upload_counts(k.f.g.get(), k.f.s, counts_colmajor, E, S, 1, 4, S, k.raw.get(), k.c.as<int32_t>())) return rc;
   // R's column-major n_bins x n_samples matrix IS the sample-major form: the aggregate references are written that way directly
   if (int rc = refcohort_impl(k.c.as<int32_t>(), E, S, bin_length, n_bins_reduced, max_refs, 0, S, n_chosen, choice, rows, correlations, nullptr,
-                              n_selected_bins, k.s, reference_out_colmajor ? k.ref.as<int32_t>() : nullptr, nullptr))
+                              n_selected_bins, k.f.s, reference_out_colmajor ? k.ref.as<int32_t>() : nullptr, nullptr))
     return rc;
-  if (reference_out_colmajor) { if (int rc = ed_d2h(reference_out_colmajor, k.ref.p, (size_t)E * S * 4, k.s)) return rc; }
+  if (reference_out_colmajor) { if (int rc = ed_d2h(reference_out_colmajor, k.ref.get(), (size_t)E * S * 4, k.f.s)) return rc; }
   return ED_OK;
 }
 ED_CATCH("ed_cohort_select_reference_sets_host")

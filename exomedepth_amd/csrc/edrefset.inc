@@ -713,12 +713,12 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
     for (int64_t e = 0; e < E; ++e)
       if (bin_length[e] == 0) return ed_fail(ED_ERR_INVALID, "bin.length contains zeros. All bin lengths must be positive");
   // ---- bin selection (R/optimize_reference_set.R:79-97) ----
-  DevBuf dtotal;
+  DevBuf<void> dtotal;
   HIP_TRY(dtotal.alloc((size_t)E * 8));
   hipLaunchKernelGGL(k_rs_rowtotal, dim3((unsigned)((E + 3) / 4)), dim3(256), 0, st, d_test, d_refs, E, R, dtotal.as<double>());
   std::vector<double> total((size_t)E);
   std::vector<int32_t> test_h((size_t)E);
-  HIP_TRY(hipMemcpyAsync(total.data(), dtotal.p, (size_t)E * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(total.data(), dtotal.get(), (size_t)E * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(test_h.data(), d_test, (size_t)E * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   int64_t n_gt2 = 0;
@@ -739,12 +739,12 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
   if (n < 2) return ed_fail(ED_ERR_STATE, "ed_select_reference_set: fewer than 2 bins selected");
   // ---- device buffers ----
   const int64_t nblk = (n + kFitChunk - 1) / kFitChunk, nchunk = nblk * kFitSub;
-  DevBuf dsel, dlen, dpart, dred, dcolsum, dcolmean, dorder, dcum, dtsel, dphi, dp, di32, dsize, dact, dbf;
+  DevBuf<void> dsel, dlen, dpart, dred, dcolsum, dcolmean, dorder, dcum, dtsel, dphi, dp, di32, dsize, dact, dbf;
   HIP_TRY(dsel.alloc((size_t)n * 4));
-  HIP_TRY(hipMemcpyAsync(dsel.p, sel.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dsel.get(), sel.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
   if (bin_length) {
     HIP_TRY(dlen.alloc((size_t)E * 8));
-    HIP_TRY(hipMemcpyAsync(dlen.p, bin_length, (size_t)E * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dlen.get(), bin_length, (size_t)E * 8, hipMemcpyHostToDevice, st));
   }
   HIP_TRY(dpart.alloc((size_t)nchunk * kRsQ * R * 8));
   HIP_TRY(dred.alloc((size_t)kRsQ * R * 8));
@@ -756,7 +756,7 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
   auto reduce_to_host = [&](int64_t cols) -> int {   // red[q * cols + r]
     hipLaunchKernelGGL(k_rs_reduce, dim3((unsigned)((cols + kWave - 1) / kWave)), bred, 0, st, dpart.as<double>(), nchunk, cols,
                        dred.as<double>());
-    HIP_TRY(hipMemcpyAsync(red.data(), dred.p, (size_t)kRsQ * cols * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(red.data(), dred.get(), (size_t)kRsQ * cols * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return ED_OK;
   };
@@ -764,7 +764,7 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
   hipLaunchKernelGGL(k_rs_colsum, gcol, bcol, 0, st, d_refs, dsel.as<int32_t>(), n, R, dpart.as<double>());
   if (int rc = reduce_to_host(R)) return rc;
   std::vector<double> colsum(red.begin(), red.begin() + R), colmean((size_t)R), corr((size_t)R);
-  HIP_TRY(hipMemcpyAsync(dcolsum.p, colsum.data(), (size_t)R * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dcolsum.get(), colsum.data(), (size_t)R * 8, hipMemcpyHostToDevice, st));
   double testsum = 0;
   for (int64_t e = 0; e < n; ++e) testsum += (double)test_h[sel[e]];
   double testmean = 0;
@@ -777,7 +777,7 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
                      dsel.as<int32_t>(), n, R, dcolsum.as<double>(), testsum, 0, (const double*)nullptr, 0.0, dpart.as<double>());
   if (int rc = reduce_to_host(R)) return rc;
   for (int64_t r = 0; r < R; ++r) colmean[r] = red[r] / (double)n;
-  HIP_TRY(hipMemcpyAsync(dcolmean.p, colmean.data(), (size_t)R * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dcolmean.get(), colmean.data(), (size_t)R * 8, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_rs_colmoments, gcol, bcol, 0, st, d_refs, d_test, bin_length ? dlen.as<double>() : nullptr,
                      dsel.as<int32_t>(), n, R, dcolsum.as<double>(), testsum, 1, dcolmean.as<double>(), testmean, dpart.as<double>());
   if (int rc = reduce_to_host(R)) return rc;
@@ -800,14 +800,14 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
   const int64_t Rw = pe - pb;   // width of the prefix window: everything below is per prefix of the window
   const dim3 gcolw((unsigned)((Rw + kWave - 1) / kWave), (unsigned)nblk), gredw((unsigned)((Rw + kWave - 1) / kWave));
   HIP_TRY(dorder.alloc((size_t)R * 4));
-  HIP_TRY(hipMemcpyAsync(dorder.p, order.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dorder.get(), order.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(dcum.alloc((size_t)n * Rw * 4));
   hipLaunchKernelGGL(k_rs_prefix, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, d_refs, dsel.as<int32_t>(),
                      dorder.as<int32_t>(), n, R, pb, pe, dcum.as<int32_t>());
   std::vector<int32_t> tsel((size_t)n);
   for (int64_t e = 0; e < n; ++e) tsel[e] = test_h[sel[e]];
   HIP_TRY(dtsel.alloc((size_t)n * 4));
-  HIP_TRY(hipMemcpyAsync(dtsel.p, tsel.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dtsel.get(), tsel.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(dphi.alloc((size_t)Rw * 8));
   HIP_TRY(dp.alloc((size_t)Rw * 8));
   {
@@ -815,19 +815,18 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
     if (int rc = w.alloc(n, Rw)) return rc;
     const int rc = fit_columns(w, dtsel.as<int32_t>(), 1, 0, dcum.as<int32_t>(), Rw, n, Rw, dphi.as<double>(), dp.as<double>(), st);
     HIP_TRY(hipStreamSynchronize(st));
-    w.release();
     if (rc) return rc;
   }
   std::vector<double> phi((size_t)Rw), pbar((size_t)Rw);
-  HIP_TRY(hipMemcpy(phi.data(), dphi.p, (size_t)Rw * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(pbar.data(), dp.p, (size_t)Rw * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(phi.data(), dphi.get(), (size_t)Rw * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(pbar.data(), dp.get(), (size_t)Rw * 8, hipMemcpyDeviceToHost));
   // ---- median(reference_i): two order statistics per column by bisection on the value ----
   const int64_t k0 = (n - 1) / 2, k1 = n / 2;
   HIP_TRY(di32.alloc((size_t)6 * Rw * 4));
   int32_t* lo0 = di32.as<int32_t>(); int32_t* hi0 = lo0 + Rw; int32_t* mid0 = hi0 + Rw;
   int32_t* lo1 = mid0 + Rw; int32_t* hi1 = lo1 + Rw; int32_t* mid1 = hi1 + Rw;
   {
-    DevBuf dpmax, dxmax;
+    DevBuf<void> dpmax, dxmax;
     HIP_TRY(dpmax.alloc((size_t)nchunk * Rw * 4));
     HIP_TRY(dxmax.alloc((size_t)Rw * 4));
     if (int rc = refset_medians(dcum.as<int32_t>(), n, Rw, k0, k1, di32.as<int32_t>(), dpart.as<double>(), dred.as<double>(), dpmax.as<int32_t>(),
@@ -835,7 +834,7 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
       return rc;
   }
   std::vector<int32_t> med((size_t)6 * Rw);
-  HIP_TRY(hipMemcpyAsync(med.data(), di32.p, med.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(med.data(), di32.get(), med.size() * 4, hipMemcpyDeviceToHost, st));
   // ---- RatioSd ----
   hipLaunchKernelGGL(k_rs_ratiosd, gcolw, bcol, 0, st, dcum.as<int32_t>(), dtsel.as<int32_t>(), n, Rw, dphi.as<double>(),
                      dpart.as<double>());
@@ -856,12 +855,12 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
   HIP_TRY(dsize.alloc((size_t)Rw * 8));
   HIP_TRY(dact.alloc((size_t)Rw * 4));
   HIP_TRY(dbf.alloc((size_t)Rw * 8));
-  HIP_TRY(hipMemcpyAsync(dsize.p, size_v.data(), (size_t)Rw * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(dact.p, active.data(), (size_t)Rw * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dsize.get(), size_v.data(), (size_t)Rw * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dact.get(), active.data(), (size_t)Rw * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_rs_power_walk, dim3((unsigned)((Rw + 3) / 4)), dim3(256), 0, st, dphi.as<double>(), dp.as<double>(), dsize.as<double>(),
                      dact.as<int>(), Rw, dbf.as<double>(), (const double*)nullptr);
   std::vector<double> bf((size_t)Rw);
-  HIP_TRY(hipMemcpyAsync(bf.data(), dbf.p, (size_t)Rw * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(bf.data(), dbf.get(), (size_t)Rw * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
   // ---- assemble: raw statistics of the window; the loop's early exit and the choice are ed_refset_finalize's ----
@@ -940,17 +939,17 @@ try {
   }
   const int64_t per_block = (int64_t)kPowBlock * kPowPer;
   const int64_t ntile = std::max<int64_t>(1, ((int64_t)max_size + 1 + per_block - 1) / per_block);
-  DevBuf dsize, dphi, dp, dalt, dact, dpow, dbf;
+  DevBuf<void> dsize, dphi, dp, dalt, dact, dpow, dbf;
   HIP_TRY(dsize.alloc((size_t)n * 8)); HIP_TRY(dphi.alloc((size_t)n * 8)); HIP_TRY(dp.alloc((size_t)n * 8));
   HIP_TRY(dalt.alloc((size_t)n * 8)); HIP_TRY(dact.alloc((size_t)n * 4)); HIP_TRY(dpow.alloc((size_t)n * ntile * 8));
   HIP_TRY(dbf.alloc((size_t)n * 8));
   std::vector<double> fl((size_t)n);
   for (int64_t i = 0; i < n; ++i) fl[i] = std::floor(size[i]);   // 0:size
-  HIP_TRY(hipMemcpy(dsize.p, fl.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dphi.p, phi, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp.p, p, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dalt.p, alt_p, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dact.p, act.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dsize.get(), fl.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dphi.get(), phi, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dp.get(), p, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dalt.get(), alt_p, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dact.get(), act.data(), (size_t)n * 4, hipMemcpyHostToDevice));
   // the default case walks the mass functions (k_rs_power_walk); parameters whose products (size x (a + b)^2) would leave binary64's range keep the
   // term-by-term form (which has long lost its digits there: differences of lnbeta values of order 1 / phi)
   bool walk = theory == 0 && max_size < 1e15;
@@ -965,7 +964,7 @@ try {
                        dbf.as<double>());
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, dbf.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, dbf.get(), (size_t)n * 8, hipMemcpyDeviceToHost));
   return ED_OK;
 }
 ED_CATCH("ed_get_power_betabinom_mode")

@@ -468,6 +468,11 @@ int ed_cohort_select_reference_sets_sm(const int32_t* d_counts, int64_t n_bins, 
 /* ed_cohort_select_reference_sets keeps its device scratch (about 1.5 GB at 10 000 selected bins x 1024 samples) between calls;
  * this returns it to the device. */
 int ed_release_scratch(void);
+/* Device and pinned host allocations the library itself holds at this moment, in every object of the process and in the two scratches, and
+ * their bytes (either pointer may be NULL).  Memory handed out by ed_malloc / ed_host_alloc belongs to the caller and is not counted.  After
+ * every object has been destroyed and ed_release_scratch() and ed_dropin_release() have been called, both figures are back where they were
+ * (tests, tools/leak_check.py: unlike the device's free memory the figures belong to this process alone). */
+void ed_live_allocations(int64_t* n, int64_t* bytes);
 /* How the last ed_cohort_select_reference_sets* call of this process formed its cumulative references' statistics (tests, diagnostics): out = {chunks
  * served by the column-major kernel (csrc/edrefcohort.inc: k_rc_column), chunks served by the row-major kernels (more than 65 535 selected bins, or counts
  * beyond the reach of the column kernel's large bins), columns that kept counts beyond their bins as values, the most Newton iterations a column took,
