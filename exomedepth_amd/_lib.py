@@ -171,6 +171,16 @@ SYMBOLS = [
     ("ed_annot_n", _i64, [_vp]),
     ("ed_annot_overlaps", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     ("ed_annot_geometry", C.c_int, [C.POINTER(_i32)]),
+    ("ed_readcount_create", C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i32, _vp, _vp, _vp, _i32]),
+    ("ed_readcount_destroy", None, [_vp]),
+    ("ed_readcount_add", C.c_int, [_vp, _i32, C.c_int, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32]),
+    ("ed_readcount_finish", C.c_int, [_vp, _i32]),
+    ("ed_readcount_copy", C.c_int, [_vp, _i32, _i32, _vp]),
+    ("ed_readcount_device_counts", _vp, [_vp]),
+    ("ed_readcount_copy_exon_major", C.c_int, [_vp, _vp]),
+    ("ed_readcount_kernel_ms", C.c_int, [_vp, C.POINTER(_dbl), C.POINTER(_dbl)]),
+    ("ed_readcount_geometry", C.c_int, [C.POINTER(_i32)]),
+    ("ed_bam_scan_records", C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
 ]
 
 

@@ -15,6 +15,7 @@ All arithmetic of the path runs on the GPU; this module only marshals buffers (n
 optionally torch CUDA tensors for device-resident inputs).
 """
 import ctypes as C
+import os
 import sys
 
 import numpy as np
@@ -1636,3 +1637,224 @@ def fit_betabin(test, reference):
     finally:
         batch.close()
         plan.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# reads per exon: getBamCounts and count.everted.reads (reference R/countBamInGranges.R)
+# ---------------------------------------------------------------------------------------------
+def readcount_geometry():
+    """{block, records_per_workgroup, lds_window, finish_block} of the counting kernels (ed_readcount_geometry): for tests placing shapes on the edges"""
+    out = (C.c_int32 * 4)()
+    check(lib().ed_readcount_geometry(out))
+    return dict(zip(("block", "records_per_workgroup", "lds_window", "finish_block"), (int(v) for v in out)))
+
+
+class _ReadCountMatrix(_RawDevice):
+    """the device count matrix of a ReadCounter, int32 (n_columns, n_exons): one row a sample -- R's column-major exon x sample matrix as it
+    lies in memory, what Cohort(emit_mode=2, counts_layout=1).submit takes as it is.  It lives as long as its counter (kept alive here)."""
+
+    def __init__(self, counter, ptr):
+        _RawDevice.__init__(self, ptr)
+        self.counter = counter
+        self.shape = (counter.n_columns, counter.n)
+        self.host_dtype = np.dtype(np.int32)
+        self.nbytes = 4 * counter.n_columns * counter.n
+
+    def to_host(self):
+        out = np.empty(self.shape, np.int32)
+        if out.nbytes:
+            check(lib().ed_memcpy_d2h(_ptr(out), self.ptr, out.nbytes))
+        return out
+
+
+class ReadCounter:
+    """Exon x sample read counts on the device (ed_readcount): exons `chromosome`, `start`, `end` as closed 1-based ranges (a BED row is
+    [start + 1, end]), 1 <= start <= end, `n_columns` samples.  add() takes a chunk of BAM record fields for one column, finish() turns the
+    chunks added into that column's counts; a column is added to and finished before the next one is begun."""
+
+    def __init__(self, chromosome, start, end, n_columns, device=0):
+        chrom = [str(c) for c in chromosome]
+        self.start, self.end = _coords(start, end)
+        if not (len(chrom) == self.start.size == self.end.size):
+            raise ValueError("chromosome, start and end must have the same length")
+        self.n = int(self.start.size)
+        self.n_columns = int(n_columns)
+        self.levels = list(dict.fromkeys(chrom))                       # first-seen order
+        self._code_of = {c: i for i, c in enumerate(self.levels)}
+        self.chrom = _i32(np.fromiter((self._code_of[c] for c in chrom), dtype=np.int32, count=self.n))
+        self._maps = {}
+        self.handle = C.c_void_p()
+        check(lib().ed_readcount_create(C.byref(self.handle), int(device), self.n, len(self.levels), _ptr(self.chrom), _ptr(self.start),
+                                        _ptr(self.end), self.n_columns))
+
+    def close(self):
+        if self.handle:
+            lib().ed_readcount_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _open(self):
+        if not self.handle:
+            raise EdError("ReadCounter is closed")
+
+    def ref_to_chrom(self, ref_names):
+        """int32 per reference sequence of a BAM header: the id of the target chromosome of that name, -1 where the exons have none"""
+        key = tuple(ref_names)
+        if key not in self._maps:
+            self._maps = {key: _i32(np.asarray([self._code_of.get(str(r), -1) for r in key], dtype=np.int32))}
+        return self._maps[key]
+
+    def add(self, column, records, ref_names, mode=0, min_mapq=20, read_width=300):
+        """one chunk of records -- (refid, pos, tlen, flag_mapq) arrays as bam.BamFile.chunks() yields them -- into `column`.
+        ref_names: the BAM header's sequence names (refid indexes them).  mode 0: getBamCounts' rule, 1: everted reads."""
+        self._open()
+        refid, pos, tlen = (_i32(records[k]).ravel() for k in range(3))
+        fm = np.ascontiguousarray(records[3], dtype=np.uint32).ravel()
+        if not (refid.size == pos.size == tlen.size == fm.size):
+            raise ValueError("the four record arrays must have the same length")
+        r2c = self.ref_to_chrom(ref_names)
+        check(lib().ed_readcount_add(self.handle, int(column), int(mode), int(refid.size), _ptr(refid), _ptr(pos), _ptr(tlen), _ptr(fm),
+                                     int(r2c.size), _ptr(r2c) if r2c.size else None, int(min_mapq), int(read_width)))
+
+    def finish(self, column):
+        self._open()
+        check(lib().ed_readcount_finish(self.handle, int(column)))
+
+    def counts(self, column0=0, n_columns=None):
+        """host int32 (n_exons, n_columns): the whole matrix, or the columns column0 .. column0 + n_columns - 1"""
+        self._open()
+        k = self.n_columns - int(column0) if n_columns is None else int(n_columns)
+        out = np.empty((max(k, 0), self.n), np.int32)
+        check(lib().ed_readcount_copy(self.handle, int(column0), k, _ptr(out)))
+        return out.T
+
+    def device_counts(self, exon_major=False):
+        """the matrix on the device, everything added and finished so far in it.  Default: the matrix where it was made, int32
+        (n_columns, n_exons), sample-major (see _ReadCountMatrix) -- what Cohort(emit_mode=2, counts_layout=1).submit takes.
+        exon_major=True: a DeviceArray int32 (n_exons, n_columns), transposed on the device (ed_readcount_copy_exon_major) -- what
+        correct_counts_using_PCA, cohort_select_reference_sets and Cohort.submit in the default layout take.  Neither touches the host."""
+        self._open()
+        if exon_major:
+            out = DeviceArray(nbytes=max(4, 4 * self.n * self.n_columns))
+            out.host_dtype, out.shape = np.dtype(np.int32), (self.n, self.n_columns)
+            check(lib().ed_readcount_copy_exon_major(self.handle, out.ptr))
+            return out
+        p = lib().ed_readcount_device_counts(self.handle)
+        if not p:
+            raise EdError("libedcore: %s" % lib().ed_last_error().decode(errors="replace"))
+        return _ReadCountMatrix(self, p)
+
+    def kernel_ms(self):
+        """(k_rcnt_bin, k_rcnt_finish) device milliseconds of this counter so far"""
+        self._open()
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib().ed_readcount_kernel_ms(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+def _bed_columns(bed_frame, bed_file):
+    """the columns of a BED frame: a mapping of column name -> values (a dict, a pandas DataFrame), or a sequence of columns; else the
+    tab-separated file, no header (read.delim(header = FALSE))"""
+    if bed_frame is None:
+        if bed_file is None:
+            raise ValueError("If no bed data frame is provided there must be a link to a bed file")
+        rows = []
+        with open(bed_file) as f:
+            for line in f:
+                line = line.rstrip("\r\n")
+                if line:
+                    rows.append(line.split("\t"))
+        if rows and min(len(r) for r in rows) < 3:
+            raise ValueError("bed_file: every line needs chromosome, start and end, tab-separated")
+        cols = [[r[k] for r in rows] for k in range(min(len(r) for r in rows))] if rows else [[], [], []]
+        cols[1] = np.asarray([int(x) for x in cols[1]], dtype=np.int64)
+        cols[2] = np.asarray([int(x) for x in cols[2]], dtype=np.int64)
+        return cols
+    if hasattr(bed_frame, "keys"):
+        return [np.asarray(bed_frame[k]) for k in list(bed_frame.keys())]
+    return [np.asarray(c) for c in bed_frame]
+
+
+def bed_targets(bed_frame=None, bed_file=None, include_chr=False, reorder=True):
+    """The target frame of getBamCounts (reorder=True, R/countBamInGranges.R:308-331) or count.everted.reads (reorder=False, :438-450), on the
+    host: dict(chromosome, start, end[, exon]).  start is the BED start + 1 (targets are closed 1-based ranges); exon is there when the frame has a
+    fourth column of text.  reorder: chromosome levels '1'..'22' first, then the other names in first-seen order, rows by start + end within a
+    chromosome, ties in input order (chromosome_order); otherwise the caller's row order stands.  include_chr prefixes 'chr' to the names."""
+    cols = _bed_columns(bed_frame, bed_file)
+    if len(cols) < 3:
+        raise ValueError("the first three columns of the bed frame must be chromosome, start, end")
+    chrom = [("chr" + str(c)) if include_chr else str(c) for c in cols[0]]
+    bstart, bend = _coords(cols[1], cols[2])
+    if not (len(chrom) == bstart.size == bend.size):
+        raise ValueError("chromosome, start and end must have the same length")
+    names = None
+    if len(cols) >= 4:
+        c4 = np.asarray(cols[3])
+        if c4.dtype.kind in "US" or (c4.dtype.kind == "O" and all(isinstance(x, str) for x in c4)):
+            names = np.asarray([str(x) for x in c4], dtype=object)
+    order = chromosome_order(chrom, bstart, bend)[0] if (reorder and len(chrom)) else np.arange(len(chrom))
+    start = bstart.astype(np.int64)[order] + 1
+    if start.size and start.max() > 2**31 - 1:
+        raise ValueError("interval coordinates must fit int32")
+    out = {"chromosome": np.asarray(chrom, dtype=object)[order], "start": start.astype(np.int32), "end": bend[order]}
+    if names is not None:
+        out["exon"] = names[order]
+    return out
+
+
+def _count_bams(frame, bam_files, mode, min_mapq, read_width, device):
+    from . import bam as _bam
+    bam_files = [bam_files] if isinstance(bam_files, (str, bytes)) or hasattr(bam_files, "__fspath__") else list(bam_files)
+    if not bam_files:
+        raise ValueError("bam_files is empty")
+    bad = np.flatnonzero((frame["start"] < 1) | (frame["end"] < frame["start"]))
+    if bad.size:
+        raise ValueError("target %d is [%d, %d] after the BED start's + 1: 1 <= start <= end wanted (a BED row needs 0 <= start < end)"
+                         % (bad[0], frame["start"][bad[0]], frame["end"][bad[0]]))
+    targets = list(dict.fromkeys(frame["chromosome"]))
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(_bam.n_threads()) as pool:
+        headers = []
+        for path in bam_files:                       # every header is checked before any device work
+            with _bam.BamFile(path, pool, batch_bytes=1 << 20) as b:
+                headers.append(b.ref_names)
+            missing = [c for c in targets if c not in set(headers[-1])]
+            if missing:
+                raise ValueError("Some sequences in the target data frame cannot be found in the header of the BAM file %s: %s"
+                                 % (path, ", ".join(missing)))
+        rc = ReadCounter(frame["chromosome"], frame["start"], frame["end"], len(bam_files), device=device)
+        try:
+            for col, path in enumerate(bam_files):
+                with _bam.BamFile(path, pool) as b:
+                    for rec in b.chunks():           # the kernels of one chunk run while the next is inflated and scanned
+                        rc.add(col, rec, b.ref_names, mode=mode, min_mapq=min_mapq, read_width=read_width)
+                rc.finish(col)
+            counts = rc.counts()
+        finally:
+            rc.close()
+    out = dict(frame)
+    for col, path in enumerate(bam_files):
+        out[os.path.basename(os.fspath(path))] = np.ascontiguousarray(counts[:, col])
+    return out
+
+
+def getBamCounts(bed_frame=None, bed_file=None, bam_files=(), index_files=None, min_mapq=20, read_width=300, include_chr=False, device=0):
+    """reference R/countBamInGranges.R:298-370: the exon x sample count frame from BAM files and a BED frame, counted on the device.
+    Returns a dict of columns in the reference's order -- chromosome, start (BED start + 1), end, exon when the frame has a fourth text column,
+    then one int32 array per basename(bam) -- with rows in the reference's order (bed_targets).  A fragment per record as include/exomedepth_amd.h
+    states it ("Reads per exon", mode 0); every target chromosome must be named in each BAM header (ValueError).  index_files is accepted and
+    ignored: the whole file is scanned, which gives the same counts.  GC content (referenceFasta) is not computed."""
+    frame = bed_targets(bed_frame, bed_file, include_chr=include_chr, reorder=True)
+    return _count_bams(frame, bam_files, 0, min_mapq, read_width, device)
+
+
+def count_everted_reads(bed_frame=None, bed_file=None, bam_files=(), index_files=None, min_mapq=20, include_chr=False, device=0):
+    """reference R/countBamInGranges.R:424-468: everted read pairs (duplication evidence) per region; as getBamCounts, but the rows keep
+    the caller's order and the rule is the everted one (mode 1: mapq >= min_mapq)."""
+    frame = bed_targets(bed_frame, bed_file, include_chr=include_chr, reorder=False)
+    return _count_bams(frame, bam_files, 1, min_mapq, 0, device)

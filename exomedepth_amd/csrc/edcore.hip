@@ -50,6 +50,7 @@
 #include "ed_fit_dev.hpp"
 #include "ed_dtab.h"
 #include "ed_own.hpp"
+#include "ed_bamscan.hpp"
 
 using edown::DevBuf;
 using edown::PinBuf;
@@ -3535,3 +3536,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edrefcohort.inc"
 #include "edpca.inc"
 #include "edannot.inc"
+#include "edreadcount.inc"

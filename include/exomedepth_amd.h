@@ -767,6 +767,61 @@ int ed_annot_overlaps(ed_annot* annot, int64_t n_q, const int32_t* q_chrom, cons
  * gives S values to a workgroup.  No result depends on any of them. */
 int ed_annot_geometry(int32_t out[4]);
 
+/* =====================================================================================
+ * Reads per exon: getBamCounts and count.everted.reads (reference R/countBamInGranges.R) -- csrc/edreadcount.inc, csrc/ed_bamscan.hpp
+ * ===================================================================================== */
+
+/* The count matrix everything else consumes, made on the device from the fields of BAM records.  Exons are closed 1-based ranges
+ * [bed.start + 1, bed.end] on chromosomes given as ids 0 .. n_chrom - 1; a record is (refID, pos, tlen, flag | mapq << 16) as BAM stores them
+ * (pos 0-based), and its chromosome is ref_to_chrom[refID] (-1, a refID outside 0 .. n_ref - 1 included: the record is ignored).  With
+ * pos1 = pos + 1 a record gives at most one fragment:
+ *   mode 0, getBamCounts (countBamInGRanges.exomeDepth, :218-243).  mapq > min_mapq (strictly) everywhere.
+ *     paired (flag & 0x1):  0x2 set; 0x4, 0x8, 0x100, 0x400 clear; tlen > 0.   Fragment [pos1, pos1 + tlen] -- one longer than the template (:227).
+ *     unpaired:             0x4, 0x100, 0x400 clear.                           Fragment [pos1, pos1 + read_width] (:241).
+ *   mode 1, everted reads (countBam.everted, :127-136).  0x1 set; 0x2, 0x100, 0x400 clear; mapq >= min_mapq (not strict); pos >= 0; |tlen| < 100000;
+ *     forward strand (0x10 clear) with tlen < 0, or reverse strand with tlen > 0.   Fragment [min(pos1, pos1 + tlen), max(pos1, pos1 + tlen)].
+ *   0x200 and 0x800 are not looked at.  Two stated deviations: a record with mapq == 255 is left out in both modes (an NA in R,
+ *   which breaks the reference's subsetting), and a record with 0x4 set is left out of the everted count.
+ * An exon's count is the number of fragments on its chromosome with frag.start <= exon.end && frag.end >= exon.start (countOverlaps, type "any",
+ * closed ranges): overlapping, nested and duplicate exons each get their own full count.  Counts are exact integers and do not depend on the order
+ * of the records or on how they were cut into chunks (two rank histograms and their scans).
+ *
+ * ed_readcount_create: exons need 1 <= start <= end and a chromosome id in [0, n_chrom), n_columns >= 1; n == 0 is valid.  The matrix
+ * int32 [n_columns][n_exons] -- one column a sample, the cohort's sample-major layout (counts_layout 1) -- starts at zero.
+ * ed_readcount_add: one chunk of records (HOST arrays) into `column`; any number of calls per column.  The chunk is staged through two pinned
+ * sets, so the upload of one part runs under the kernel of the part before; the call returns when the last part has been queued.
+ * ED_ERR_INVALID before any device work: column out of range, mode not 0 / 1, read_width < 0, a ref_to_chrom entry outside -1 .. n_chrom - 1.
+ * n_records == 0 is valid.  Chunks are collected for ONE column at a time: adding to another column before ed_readcount_finish is ED_ERR_STATE.
+ * ed_readcount_finish: the collected chunks are ADDED to counts[column][:] (a column finished twice holds the sum) and the histograms are cleared;
+ * with nothing added it does nothing.  ed_readcount_copy: columns column0 .. column0 + n_columns - 1 to the host, [n_columns][n_exons];
+ * ED_ERR_STATE if one of them has chunks added and not finished.  ed_readcount_device_counts: the device matrix itself, everything queued complete.
+ * ed_readcount_kernel_ms: device time of the object's k_rcnt_bin launches and of its k_rcnt_finish launches so far (waits for them).
+ * An object is not for two threads at a time; it sets its device on every call. */
+typedef struct ed_readcount ed_readcount;
+int ed_readcount_create(ed_readcount** rc, int device, int64_t n_exons, int32_t n_chrom, const int32_t* chrom, const int32_t* start,
+                        const int32_t* end, int32_t n_columns);
+void ed_readcount_destroy(ed_readcount* rc);
+int ed_readcount_add(ed_readcount* rc, int32_t column, int mode, int64_t n_records, const int32_t* refid, const int32_t* pos,
+                     const int32_t* tlen, const uint32_t* flag_mapq, int32_t n_ref, const int32_t* ref_to_chrom, int32_t min_mapq,
+                     int32_t read_width);
+int ed_readcount_finish(ed_readcount* rc, int32_t column);
+int ed_readcount_copy(ed_readcount* rc, int32_t column0, int32_t n_columns, int32_t* out);
+void* ed_readcount_device_counts(ed_readcount* rc);
+/* the matrix transposed into the caller's DEVICE array int32 [n_exons][n_columns] -- the exon-major form ed_correct_counts_pca and
+ * ed_cohort_select_reference_sets read -- device to device, complete on return; ED_ERR_STATE while a column has chunks added and not finished */
+int ed_readcount_copy_exon_major(ed_readcount* rc, int32_t* d_out);
+int ed_readcount_kernel_ms(ed_readcount* rc, double* bin_ms, double* finish_ms);
+/* Launch geometry, for tests that place their shapes on its edges: out = {B, R, W, F}.  k_rcnt_bin has B threads a workgroup, which take R records;
+ * W is the width in bins of a workgroup-private histogram window (0: there is none); k_rcnt_finish scans F values a step.  No result depends on them. */
+int ed_readcount_geometry(int32_t out[4]);
+/* Host only, no device needed: the records of buf[0, n_bytes) -- a piece of an INFLATED BAM stream that starts at a record boundary (after the
+ * header) -- at most cap of them: refID, pos, tlen and flag | mapq << 16 of each.  The scan follows the block_size chain and stops before the
+ * first record that is not wholly inside the buffer; *bytes_consumed is then that record's offset (always a record boundary), and the caller
+ * carries the rest into its next buffer.  A block_size below 32 or above 2^28 (a negative one included): ED_ERR_INVALID with a message that
+ * names the record; *n_records and *bytes_consumed then describe the records before it.  No byte outside the buffer is read. */
+int ed_bam_scan_records(const uint8_t* buf, int64_t n_bytes, int64_t cap, int32_t* refid, int32_t* pos, int32_t* tlen, uint32_t* flag_mapq,
+                        int64_t* n_records, int64_t* bytes_consumed);
+
 /* ---- utilities ---- */
 /* device memory through the library, for callers without a HIP binding (tests, R shim) */
 int ed_malloc(void** dptr, size_t bytes);
