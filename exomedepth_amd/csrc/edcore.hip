@@ -51,6 +51,7 @@
 #include "ed_dtab.h"
 #include "ed_own.hpp"
 #include "ed_bamscan.hpp"
+#include "ed_launch_plan.hpp"
 
 using edown::DevBuf;
 using edown::PinBuf;
@@ -123,9 +124,7 @@ static int require_device()
 // ------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int kEmitBlock = 256;
 constexpr int kEmitTab = 1024;   // test counts covered by the per-sample tables (k_emit_tables)
-constexpr uint32_t kEmitRun = 256;   // exon blocks an XCD spends on one sample block before taking up the next (k_emit_batch)
 constexpr int kWave = 64;
 
 // myprob's shape parameters for one state (src/CNV_estimate.cpp:45-46)
@@ -249,11 +248,7 @@ __device__ __forceinline__ void ed_buf_store_f64_nt(__amdgpu_buffer_rsrc_t r, ui
 // array, all others from the back, so every wave of the evaluation phase but at most one runs a
 // single route.  Cells are numbered exon-major / sample-minor: a wave reads 64 consecutive samples of
 // one exon (coalesced) and writes three coalesced rows of the [E][3][S] likelihood matrix.
-constexpr int kEmitCells = 1;                                // cells per thread
 constexpr int kEmitTasks = kEmitBlock * kEmitCells * 3;      // tasks per workgroup
-constexpr int kEmitRows = kEmitCells * kEmitBlock / 64;      // exons per workgroup tile (x 64 samples)
-constexpr int64_t kEmitHeadBlocks = 2048;                    // workgroups of a group's short leading launch (ed_batch_run)
-constexpr int kSideStreams = 3;                              // HIP maps streams onto 4 hardware queues: main + 3
 
 // the portable log's table as a device global: staged into LDS by one load per thread (SGPR base + lane offset)
 __device__ const double k_logt_rows[ED_PM_LOGT_N][3] = ED_PM_LOGT_ROWS;
@@ -679,8 +674,6 @@ k_emit_verify(const int32_t* __restrict__ test, const int32_t* __restrict__ ref,
 // (0,-inf,-inf) (src/hmm.cpp:48-52; the first dummy row is never read) and ends with one extra step
 // whose emissions are (-100, 0, -100).
 constexpr int kVitTile = 16;      // steps per back-pointer / packed-state word
-
-constexpr int kVitChains = 16;    // chains per wave
 
 template <int K>
 __device__ __forceinline__ double quad_bcast(double x)
@@ -1829,11 +1822,12 @@ struct ed_batch {
   int64_t tab_stride = 0;        // entries between the tables of consecutive samples = 2 (capY + capR)
   TabSet tab;
   unsigned int cold_cap = 0;
-  std::vector<int64_t> seg_t;    // emission segments for k_emit_tab's tile shape (as `seg`)
+  std::vector<int64_t> seg_t;    // emission segments for k_emit_tab's tile shape (as `seg`; host tables of every mode are made by ed_batch_create)
   // emit mode 2: the documented [E][3][S] form (d_loglik) is made from the sample-major matrix when an accessor asks (rows_valid)
   SmSet sm;
   int64_t Epad = 0;
   std::vector<int64_t> seg_sm;   // segments in blocks of 64 exons (first block, first exon, end exon), job order
+  std::vector<edplan::Block> blk_sm;   // ... and the blocks themselves (host copy of sm.d_blk_sm; never empty)
   int vit_waves = 1024;          // waves of that grid: the SIMDs of the device (tab_setup_sm)
   int64_t nblk_sm = 0;
   bool rows_valid = true;
@@ -2184,80 +2178,14 @@ try {
     // emissions group by group; the Viterbi chains of a group start on a side stream as soon as that
     // group's emissions are done and run underneath the (VALU-bound) emissions of the following groups.
     // Groups shrink geometrically so that the last, exposed Viterbi launch only holds short chains.
-    std::vector<int> order;
-    int64_t total = 0;
-    for (int c = 0; c < (int)C; ++c) {
-      const int64_t mc = plan->chrom_off[c + 1] - plan->chrom_off[c];
-      if (mc > 0) { order.push_back(c); total += mc; }
-    }
-    std::sort(order.begin(), order.end(), [&](int a, int bb) {
-      const int64_t la = plan->chrom_off[a + 1] - plan->chrom_off[a], lb = plan->chrom_off[bb + 1] - plan->chrom_off[bb];
-      return la != lb ? la > lb : a < bb; });
+    const std::vector<int> order = edplan::job_order(plan->chrom_off);
     std::vector<std::vector<int>> jobs;
-    for (int c : order) jobs.push_back(std::vector<int>(1, c));
-    // How to cut the jobs (longest chromosome first) into groups?  A group's Viterbi runs on a side stream as soon
-    // as the group's emissions are done.  HIP multiplexes streams onto 4 hardware queues, and streams that share
-    // a queue serialise (seen in the kernel trace: with 7 side streams the emissions themselves waited behind
-    // Viterbi kernels), so there are kSideStreams = 3 side streams, used round-robin; a group's chains finish at
-    // max(its emissions done, its stream free) + (its longest chain) -- slower when the resident Viterbi waves
-    // outnumber the SIMDs.
-    // Small batches want the long chromosomes in groups of their own, issued first, so that their chains start
-    // early; large batches want few groups (every group boundary costs a short extra launch and the tail of
-    // an emission launch).  A two-constant cost model picks among a handful of cut sets (measured on MI355X:
-    // emissions 5.4e-11 s per cell; 6.5e-8 s per chain step, forward + trace-back).
+    std::vector<int64_t> len;
+    for (int c : order) { jobs.push_back(std::vector<int>(1, c)); len.push_back(plan->chrom_off[c + 1] - plan->chrom_off[c]); }
+    // the groups: the cheapest of a handful of cut sets under a two-constant cost model (ed_launch_plan.hpp: choose_groups)
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, plan->device));
-    const double simds = 4.0 * prop.multiProcessorCount;
-    const double c_emit = 5.4e-11, c_step = 6.5e-8, c_launch = 1.5e-5;
-    const int32_t J = (int32_t)jobs.size();
-    std::vector<std::vector<int32_t>> candidates;
-    auto by_fraction = [&](const std::vector<double>& cuts) {
-      std::vector<int32_t> goff(1, 0);
-      int64_t run = 0;
-      size_t gi = 0;
-      for (int32_t k = 0; k < J; ++k) {
-        run += plan->chrom_off[jobs[k][0] + 1] - plan->chrom_off[jobs[k][0]];
-        while (gi + 1 < cuts.size() && (double)run >= cuts[gi] * (double)total && k + 1 < J) {
-          if (k + 1 > goff.back()) goff.push_back(k + 1);
-          ++gi;
-        }
-      }
-      if (goff.back() != J) goff.push_back(J);
-      return goff;
-    };
-    auto by_index = [&](std::vector<int32_t> idx) {
-      std::vector<int32_t> goff(1, 0);
-      for (int32_t v : idx) if (v > goff.back() && v < J) goff.push_back(v);
-      if (goff.back() != J) goff.push_back(J);
-      return goff;
-    };
-    candidates.push_back(by_fraction({1.0}));
-    candidates.push_back(by_fraction({0.55, 1.0}));
-    candidates.push_back(by_fraction({0.40, 0.72, 0.90, 1.0}));
-    candidates.push_back(by_index({1}));
-    candidates.push_back(by_index({1, 3}));
-    candidates.push_back(by_index({1, 3, 8}));
-    candidates.push_back(by_index({1, 2, 4, 10}));
-    double best_cost = 1e300;
-    for (const auto& goff : candidates) {
-      double t_main = 0.0, finish = 0.0, waves = 0.0;
-      double busy[kSideStreams] = {0.0, 0.0, 0.0};   // when each side stream becomes free
-      for (size_t g = 0; g + 1 < goff.size(); ++g) {
-        int64_t exons = 0, longest = 0;
-        for (int k = goff[g]; k < goff[g + 1]; ++k) {
-          const int64_t mc = plan->chrom_off[jobs[k][0] + 1] - plan->chrom_off[jobs[k][0]];
-          exons += mc; longest = std::max(longest, mc);
-        }
-        t_main += c_emit * (double)exons * (double)S + (g > 0 ? c_launch : 0.0);
-        waves += (double)(goff[g + 1] - goff[g]) * std::ceil((double)S / kVitChains);   // (earlier groups still running)
-        const double vit = c_step * (double)longest * std::max(1.0, waves / (2.0 * simds));
-        double& q = busy[g % kSideStreams];
-        q = std::max(q, t_main) + vit;
-        finish = std::max(finish, q);
-      }
-      const double cost = std::max(t_main, finish);
-      if (cost < best_cost) { best_cost = cost; b->group_off = goff; }
-    }
+    b->group_off = edplan::choose_groups(len, S, 4.0 * prop.multiProcessorCount);
     b->group_off_model = b->group_off;
     std::vector<int32_t> joff(1, 0), jchr;
     for (auto& jb : jobs) { for (int c : jb) jchr.push_back(c); joff.push_back((int32_t)jchr.size()); }
@@ -2275,18 +2203,16 @@ try {
     HIP_TRY(b->d_job_chrom.alloc(std::max<size_t>(jchr.size(), 1) * 4));
     HIP_TRY(hipMemcpy(b->d_job_off, joff.data(), joff.size() * 4, hipMemcpyHostToDevice));
     if (!jchr.empty()) HIP_TRY(hipMemcpy(b->d_job_chrom, jchr.data(), jchr.size() * 4, hipMemcpyHostToDevice));
-    // emission segments: one per job (= chromosome), in job order, so that a whole group is ONE launch
-    int64_t blk = 0;
-    for (auto& jb : jobs) {
-      const int c = jb[0];
-      const int64_t eb = plan->chrom_off[c], ee = plan->chrom_off[c + 1];
-      b->seg.push_back(blk); b->seg.push_back(eb); b->seg.push_back(ee);
-      {
-        const int64_t neb = (ee - eb + kEmitRows - 1) / kEmitRows, nsb = (S + 63) / 64;
-        blk += (nsb >= 8) ? ((neb + kEmitRun - 1) / kEmitRun) * (int64_t)kEmitRun * 8 * ((nsb + 7) / 8) : neb * nsb;
-      }
-    }
-    b->seg.push_back(blk); b->seg.push_back(0); b->seg.push_back(0);
+    // emission segments: one per job (= chromosome), in job order, so that a whole group is ONE launch -- for each mode's workgroups
+    // (host tables only: the table modes upload theirs when their buffers are made, tab_setup / tab_setup_sm)
+    b->seg = edplan::segments(edplan::kSegStrict, plan->chrom_off, order, S).seg;
+    b->seg_t = edplan::segments(edplan::kSegTile, plan->chrom_off, order, S).seg;
+    edplan::SegTable sm = edplan::segments(edplan::kSegSm, plan->chrom_off, order, S);
+    b->seg_sm = std::move(sm.seg);
+    b->blk_sm = std::move(sm.blocks);
+    if (b->blk_sm.empty()) b->blk_sm.push_back(edplan::Block{0, 0});
+    b->nblk_sm = (int64_t)b->blk_sm.size();
+    b->Epad = edplan::sm_epad(E);
     HIP_TRY(b->d_seg.alloc(b->seg.size() * 8));
     HIP_TRY(hipMemcpy(b->d_seg, b->seg.data(), b->seg.size() * 8, hipMemcpyHostToDevice));
   }
@@ -2431,18 +2357,6 @@ static int tab_setup(ed_batch* b)
   // (a sixteenth of the cells: the lists of round 5 -- a thirty-second -- ran out at 1 600 reads per exon, where 2 % of the cells lie beyond the conditioning limit,
   //  and the strict pass then walked all 2 x 10^8 cells again: 7.6 ms)
   b->cold_cap = (unsigned int)std::min<int64_t>(std::max<int64_t>(E * S / 16, 1 << 16), (int64_t)1 << 28) / kColdLists * kColdLists;
-  // segments in job order, workgroups numbered for k_emit_tab's tile (rows x kTabTw samples), as ed_batch_create does for k_emit_batch
-  const int64_t rows = 4 * (64 / kTabTw), nsb = (S + kTabTw - 1) / kTabTw;
-  int64_t blk = 0;
-  b->seg_t.clear();
-  for (auto& jb : b->jobs) {
-    const int c = jb[0];
-    const int64_t eb = p->chrom_off[c], ee = p->chrom_off[c + 1];
-    b->seg_t.push_back(blk); b->seg_t.push_back(eb); b->seg_t.push_back(ee);
-    const int64_t neb = (ee - eb + rows - 1) / rows;
-    blk += (nsb >= 8) ? ((neb + kTabRun - 1) / kTabRun) * (int64_t)kTabRun * 8 * ((nsb + 7) / 8) : neb * nsb;
-  }
-  b->seg_t.push_back(blk); b->seg_t.push_back(0); b->seg_t.push_back(0);
   TabSet t;
   bool ok = true;
   auto A = [&](auto& buf, size_t bytes) { if (ok && buf.alloc(bytes) != hipSuccess) ok = false; };
@@ -2474,25 +2388,8 @@ static int tab_setup_sm(ed_batch* b)
   if (b->sm.made()) return ED_OK;
   const ed_plan* p = b->plan;
   const int64_t S = b->S, E = p->E;
-  b->Epad = ((E + 15) / 16) * 16 + 96;    // (k_viterbi_sm loads whole tiles up to four tiles past a chromosome's end)
-  // Blocks of 64 exons on the ABSOLUTE exon grid, clipped to their chromosome: every block but the first and last of a chromosome
-  // starts at a multiple of 64 exons, so that a wave's three 512-byte stores are whole aligned 128-byte lines of the [S][3][Epad]
-  // matrix (chromosome-relative blocks made nearly every store begin and end with a partial line).
-  int64_t blk = 0;
-  b->seg_sm.clear();
-  std::vector<int2> bm;
-  for (auto& jb : b->jobs) {
-    const int c = jb[0];
-    const int64_t eb = p->chrom_off[c], ee = p->chrom_off[c + 1];
-    b->seg_sm.push_back(blk); b->seg_sm.push_back(eb); b->seg_sm.push_back(ee);
-    for (int64_t q = (eb / 64) * 64; q < ee; q += 64) {
-      bm.push_back(make_int2((int)std::max(q, eb), (int)std::min(q + 64, ee)));
-      ++blk;
-    }
-  }
-  b->seg_sm.push_back(blk); b->seg_sm.push_back(0); b->seg_sm.push_back(0);
-  if (bm.empty()) bm.push_back(make_int2(0, 0));
-  b->nblk_sm = (int64_t)bm.size();
+  const std::vector<edplan::Block>& bm = b->blk_sm;   // blocks of 64 exons on the absolute exon grid (ed_launch_plan.hpp: segments)
+  static_assert(sizeof(edplan::Block) == sizeof(int2), "the block map is uploaded as the kernels' int2");
   SmSet t;
   bool ok = true;
   auto A = [&](auto& buf, size_t bytes) { if (ok && buf.alloc(bytes) != hipSuccess) ok = false; };
@@ -2578,13 +2475,32 @@ static int tab_build(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, h
   else if (E > 0)
     hipLaunchKernelGGL(k_tab_stats, dim3((unsigned)((S + 63) / 64), (unsigned)((E + 64 * step - 1) / (64 * step))), dim3(256), 0, st, d_test, d_ref, E, S,
                        step, b->tab.d_tacc);
-  if (S < 256)
-    hipLaunchKernelGGL(k_tab_build<256>, dim3((unsigned)S, 3), dim3(256), 0, st, b->d_consts, b->d_cflags, b->tab.d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
-                       b->tab.d_tdims, S, b->tab.d_tabs, b->tab_stride, b->tab.d_notab, tails, b->tab.d_twins, b->tab.d_tlg0);
-  else
-    hipLaunchKernelGGL(k_tab_build<64>, dim3((unsigned)S, 3), dim3(64), 0, st, b->d_consts, b->d_cflags, b->tab.d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
-                       b->tab.d_tdims, S, b->tab.d_tabs, b->tab_stride, b->tab.d_notab, tails, b->tab.d_twins, b->tab.d_tlg0);
+  const auto build = S < 256 ? k_tab_build<256> : k_tab_build<64>;
+  hipLaunchKernelGGL(build, dim3((unsigned)S, 3), dim3(S < 256 ? 256 : 64), 0, st, b->d_consts, b->d_cflags, b->tab.d_tacc, b->tab_reach, b->tab_capY, b->tab_capR,
+                     b->tab.d_tdims, S, b->tab.d_tabs, b->tab_stride, b->tab.d_notab, tails, b->tab.d_twins, b->tab.d_tlg0);
   HIP_TRY(hipGetLastError());
+  return ED_OK;
+}
+
+// The per-sample constants (k_sample_consts) and, outside fused mode, the tables made from them: the log-gamma difference tables of the
+// table modes (tab_build) or k_emit_tables.  k_sample_consts also zeroes the table modes' counters, and with zero_nerr the run's error
+// counters.  (phi, expected) are read from the cohort pipeline's source arrays when it has set them, and copied to the arrays handed over.
+static int consts_and_tables(ed_batch* b, const double* d_phi, const double* d_expected, double mixture, hipStream_t st, const int32_t* d_test,
+                             const int32_t* d_ref, bool zero_nerr)
+{
+  const int64_t S = b->S;
+  const bool tabm = b->emit_mode >= 1 && !b->fused;
+  if (tabm) { if (int rc = tab_setup(b)) return rc; }
+  const bool from_src = b->src_phi && b->src_exp;
+  hipLaunchKernelGGL(k_sample_consts, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, from_src ? b->src_phi : d_phi, from_src ? b->src_exp : d_expected, mixture, S,
+                     b->d_consts, b->d_cflags, zero_nerr ? b->d_nerr : (unsigned long long*)nullptr, tabm ? b->tab.d_tacc : (unsigned long long*)nullptr,
+                     tabm ? b->tab.d_notab : (unsigned int*)nullptr, tabm ? b->tab.d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
+                     from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr, b->d_mix);
+  b->src_phi = b->src_exp = nullptr;
+  if (tabm) return tab_build(b, d_test, d_ref, st);
+  if (!b->fused)
+    hipLaunchKernelGGL(k_emit_tables, dim3((unsigned)((S + 63) / 64), (unsigned)(kEmitTab / 4), 3), dim3(256), 0, st, b->d_consts, S, b->d_tab_gl,
+                       b->d_tab_lg);
   return ED_OK;
 }
 
@@ -2599,23 +2515,300 @@ static int batch_prepare(ed_batch* b, const double* d_phi, const double* d_expec
 {
   if (b->fused) return ED_OK;
   if (b->emit_mode >= 1 && (!d_test || !d_ref)) return ED_OK;   // the tables need the counts: made by the run itself
-  const int64_t S = b->S;
-  if (b->emit_mode >= 1) { if (int rc = tab_setup(b)) return rc; }
-  // (the error / table counters of the batch's previous run may not have been read yet: they are zeroed by the run itself)
-  const bool from_src = b->src_phi && b->src_exp;
-  hipLaunchKernelGGL(k_sample_consts, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, from_src ? b->src_phi : d_phi, from_src ? b->src_exp : d_expected, mixture, S,
-                     b->d_consts, b->d_cflags,
-                     zero_counters ? b->d_nerr : (unsigned long long*)nullptr, b->emit_mode >= 1 ? b->tab.d_tacc : (unsigned long long*)nullptr,
-                     b->emit_mode >= 1 ? b->tab.d_notab : (unsigned int*)nullptr, b->emit_mode >= 1 ? b->tab.d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
-                     from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr, b->d_mix);
-  b->src_phi = b->src_exp = nullptr;
+  // (the error / table counters of the batch's previous run may not have been read yet: they are zeroed by the run itself
+  //  unless the caller says otherwise)
+  const int rc = consts_and_tables(b, d_phi, d_expected, mixture, st, d_test, d_ref, zero_counters);
   b->prepared_zeroed = zero_counters;
-  if (b->emit_mode >= 1) { if (int rc = tab_build(b, d_test, d_ref, st)) return rc; }
-  else
-  hipLaunchKernelGGL(k_emit_tables, dim3((unsigned)((S + 63) / 64), (unsigned)(kEmitTab / 4), 3), dim3(256), 0, st, b->d_consts, S, b->d_tab_gl,
-                     b->d_tab_lg);
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   b->prepared = true; b->prepared_phi = d_phi; b->prepared_exp = d_expected; b->prepared_mix = mixture; b->prepared_mix_s = b->d_mix;
+  return ED_OK;
+}
+
+// ---- ed_batch_run: a short sequence of stages (batch_run_impl, below).  How the work is cut into launches -- segments, groups, the
+// head / cut / rest pieces of a group, grids -- is ed_launch_plan.hpp's; the stages only issue what it says, in stream order. ----
+
+// One run: its arguments and what follows from them and from the batch's settings, made once by run_open and read by every stage.
+struct Run {
+  ed_batch* b;
+  const int32_t* d_test; const int32_t* d_ref;
+  const double* d_phi; const double* d_expected;
+  double mixture;
+  const EmitModel* em;
+  bool plain;          // per-sample (phi, expected): k_emit_batch with hoisted constants
+  bool tabm;           // emissions from log-gamma difference tables (edtab.inc)
+  bool tabsm;          // ... sample-major form: tables in LDS, [S][3][Epad] likelihood matrix
+  bool cl1;            // counts handed over sample-major [S][E]
+  int cb;              // bytes per count
+  bool async;
+  hipStream_t st;      // the caller's stream
+  hipStream_t tail;    // where the call table is built and the results become available
+};
+
+static edplan::SegKind seg_kind(int emit_mode) { return emit_mode == 2 ? edplan::kSegSm : (emit_mode == 1 ? edplan::kSegTile : edplan::kSegStrict); }
+static const std::vector<int64_t>& seg_of(const ed_batch* b, edplan::SegKind kind)
+{
+  return kind == edplan::kSegSm ? b->seg_sm : (kind == edplan::kSegTile ? b->seg_t : b->seg);
+}
+
+// checks, derived flags, and the state a run leaves on the batch whatever becomes of it
+static int run_open(Run& r, ed_batch* b, const int32_t* d_test, const int32_t* d_ref, const double* d_phi, const double* d_expected, double mixture,
+                    void* stream_, const EmitModel& em)
+{
+  r.plain = (em.bins == 0 && !em.cov);
+  if (!b || !d_test || !d_ref || !d_phi || !d_expected) return ed_fail(ED_ERR_INVALID, "ed_batch_run: NULL argument");
+  if (!r.plain && b->fused) return ed_fail(ED_ERR_STATE, "ed_batch_run_bins / _cov: not available in fused mode");
+  r.b = b; r.d_test = d_test; r.d_ref = d_ref; r.d_phi = d_phi; r.d_expected = d_expected; r.mixture = mixture; r.em = &em;
+  r.tabm = r.plain && b->emit_mode >= 1 && !b->fused;
+  r.tabsm = r.tabm && b->emit_mode == 2;
+  b->rows_valid = !r.tabsm;
+  b->path_valid = kEagerPath && !b->fused;   // the byte path is made when it is asked for (ensure_path)
+  r.cl1 = b->counts_layout == 1;
+  if (r.cl1 && !r.tabsm) return ed_fail(ED_ERR_STATE, "ed_batch_run: sample-major counts (ed_batch_set_counts_layout(batch, 1)) are served by emit mode 2 only");
+  if (b->counts_bits == 16 && !(r.cl1 && r.tabsm)) return ed_fail(ED_ERR_STATE, "ed_batch_run: 16-bit counts (ed_batch_set_counts_bits(batch, 16)) are served by counts_layout 1 + emit mode 2 only");
+  r.cb = b->cb();
+  HIP_TRY(hipSetDevice(b->plan->device));   // the caller's thread may have another device current (one process, many GPUs)
+  r.st = (hipStream_t)stream_;
+  r.async = b->async_tail && !b->fused;
+  r.tail = r.async ? b->fin : r.st;
+  if (b->timing) { if (int rc = fold_run_times(b)) return rc; }
+  // the previous run's asynchronous tail still reads the buffers -- whatever the mode of THIS run (ADVICE r2)
+  if (b->ran && b->last_run_async && b->done_ev) HIP_TRY(hipStreamWaitEvent(r.st, b->done_ev, 0));
+  b->stream = r.tail;
+  b->split_recorded = false;
+  b->last_test = d_test; b->last_ref = d_ref; b->last_expected = d_expected; b->last_layout = b->counts_layout; b->last_cb = r.cb;
+  b->last_cov_X = em.cov ? em.X : nullptr; b->last_cov_K = em.cov ? em.K : -1; b->last_cov_beta = em.cov ? em.beta : nullptr;
+  return ED_OK;
+}
+
+// the run's counters zeroed, and the constants and tables unless batch_prepare made them from the same parameters
+static int run_consts(const Run& r)
+{
+  ed_batch* b = r.b;
+  // (the preparation is made by the same submission right before this run -- b->prepared is cleared below -- so a caller that rewrites the
+  // per-sample mixtures behind the same pointer between two runs always gets fresh constants)
+  const bool ready = r.plain && b->prepared && b->prepared_phi == r.d_phi && b->prepared_exp == r.d_expected && b->prepared_mix == r.mixture &&
+                     b->prepared_mix_s == b->d_mix && !b->fused;
+  b->prepared = false;
+  if (!r.plain || (ready && !b->prepared_zeroed)) HIP_TRY(hipMemsetAsync(b->d_nerr, 0, 64, r.st));     // (otherwise: k_sample_consts, below or in batch_prepare)
+  b->prepared_zeroed = false;
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[0], r.st));
+  if (r.plain && !ready) return consts_and_tables(b, r.d_phi, r.d_expected, r.mixture, r.st, r.d_test, r.d_ref, true);
+  return ED_OK;
+}
+
+// emit mode 2: the counts sample-major (R's own layout; with ed_batch_set_counts_layout(batch, 1) they arrive that way)
+static int run_transpose(const Run& r)
+{
+  ed_batch* b = r.b;
+  const int64_t E = b->plan->E, S = b->S;
+  if (!r.tabsm) return ED_OK;
+  if (int rc = tab_setup_sm(b)) return rc;
+  if (E > 0 && !r.cl1) {
+    const dim3 tg((unsigned)((E + 63) / 64), (unsigned)((S + 63) / 64));
+    hipLaunchKernelGGL(k_tab_rows_to_cols, tg, dim3(256), 0, r.st, r.d_test, E, S, b->sm.d_test_sm);
+    hipLaunchKernelGGL(k_tab_rows_to_cols, tg, dim3(256), 0, r.st, r.d_ref, E, S, b->sm.d_ref_sm);
+  }
+  return ED_OK;
+}
+
+// One fused launch: every workgroup owns 16 samples x one chromosome (longest chromosomes first) and runs
+// emissions and Viterbi together (edfused.inc); the likelihood matrix is written only if it is kept.
+static int run_fused(const Run& r)
+{
+  ed_batch* b = r.b;
+  const ed_plan* p = b->plan;
+  const int64_t E = p->E, S = b->S;
+  const int32_t C = p->C;
+  HIP_TRY(hipMemsetAsync(b->d_counts, 0, (size_t)S * std::max<int64_t>(C, 1) * 4, r.st));   // empty chromosomes: no calls
+  if (b->keep_loglik && !b->d_loglik) {
+    if (b->d_loglik.alloc((size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
+      return ed_fail(ED_ERR_NOMEM, "ed_batch_run: cannot allocate the likelihood matrix (%lld bytes)", (long long)(E * 3 * S * 8));
+  }
+  if (E * S > 0 && b->n_jobs > 0)
+    hipLaunchKernelGGL(k_emit_viterbi, dim3((unsigned)((S + kFuS - 1) / kFuS), (unsigned)b->n_jobs), dim3(kFuBlock), 0, r.st,
+                       r.d_test, r.d_ref, b->d_consts, b->d_cflags, p->d_lt3, p->c0, p->c1, p->d_chrom_off, p->d_tile_off, S, C,
+                       b->keep_loglik ? b->d_loglik : (double*)nullptr, b->d_bp, b->d_ppath, b->d_counts, b->d_job_off,
+                       b->d_job_chrom, b->d_nerr);
+  return ED_OK;
+}
+
+// the depth-binned / covariate models: one launch over every cell (cut into pieces for the cohort pipeline); the Viterbi groups follow it
+static int run_model_emissions(const Run& r)
+{
+  ed_batch* b = r.b;
+  const EmitModel& em = *r.em;
+  const int64_t E = b->plan->E, S = b->S;
+  const int64_t eblk = (E + kEmitBlock / 64 - 1) / (kEmitBlock / 64);   // 4 exons x 64 samples per workgroup
+  auto grid = [&](int64_t n) { const edplan::Fold f = edplan::fold(n); return dim3((unsigned)((S + 63) / 64), f.y, f.z); };
+  const double* ctab = nullptr;
+  if (em.bins > 0 && !em.cov) {
+    // depth-binned dispersion: the constants lbeta(a1, a2) per (sample, state, reference count) first, then three tasks per cell
+    const dim3 egrid = grid(eblk);
+    if (int rc = bins_ctab_setup(b, (size_t)egrid.x * egrid.y * egrid.z)) return rc;
+    hipLaunchKernelGGL(k_bins_ctab, dim3((unsigned)((S + 63) / 64), (unsigned)(kBinsRtab / 4)), dim3(256), 0, r.st, em.bins, em.edges, r.d_phi, r.d_expected,
+                       r.mixture, S, kBinsRtab, b->ctab.d_ctab, em.skip, b->d_mix);
+    // In the cohort pipeline the launch is cut into pieces: the NEXT slab's fit consists of several kernels whose workgroups need a
+    // (nearly) whole CU each, and such a workgroup only gets one at a launch boundary, where the CUs drain -- under one uncut
+    // launch the 3.5-ms fit took the launch's whole 13.8 ms and then stood between two emission launches.
+    const int pieces = (int)std::max<int64_t>(1, std::min<int64_t>(b->bins_pieces, eblk));
+    for (int pc = 0; pc < pieces; ++pc) {
+      const int64_t pb0 = edplan::piece_begin(eblk, pc, pieces), pn = edplan::piece_begin(eblk, pc + 1, pieces) - pb0;
+      if (pn <= 0) continue;
+      hipLaunchKernelGGL(k_emit_bins_tab, grid(pn), dim3(kEmitBlock), 0, r.st, r.d_test, r.d_ref, em.bins, em.edges, r.d_phi, r.d_expected, r.mixture, E, S,
+                         b->ctab.d_ctab, kBinsRtab, b->d_loglik, b->ctab.d_left_out, em.skip, pb0, pn, b->d_mix);
+    }
+    ctab = b->ctab.d_ctab;
+  }
+  const int tpw = ctab ? 32 : 1;   // behind the tabulated kernel nearly every tile returns on one byte (1 / 8 / 32 on one box: 17.0 / 16.2 / 16.1 ms per slab)
+  hipLaunchKernelGGL(k_emit_bins, grid((eblk + tpw - 1) / tpw), dim3(kEmitBlock), 0, r.st, r.d_test, r.d_ref, em.bins, em.edges, r.d_phi,
+                     em.cov ? (const double*)nullptr : r.d_expected, em.X, em.cov ? em.K : -1, em.beta, r.mixture, E, S, b->d_loglik,
+                     b->d_nerr, ctab, kBinsRtab, b->ctab.d_left_out, em.skip, tpw, eblk, b->d_mix);
+  return ED_OK;
+}
+
+// one emission launch of the per-sample model over workgroups [base, base + n) of the mode's numbering
+static void emit_launch(const Run& r, int64_t n, int64_t base)
+{
+  ed_batch* b = r.b;
+  const int64_t E = b->plan->E, S = b->S;
+  if (r.tabsm) {    // n, base: blocks of 64 exons; every sample gets nsplit workgroups that share them
+    const edplan::SmGrid g = edplan::sm_grid(S, n);
+    const auto emit = (r.cl1 && r.cb == 2) ? k_emit_tab_sm<2> : k_emit_tab_sm<4>;
+    hipLaunchKernelGGL(emit, dim3((unsigned)g.nwg), dim3(kSmBlock), 0, r.st, r.cl1 ? r.d_test : b->sm.d_test_sm, r.cl1 ? r.d_ref : b->sm.d_ref_sm, b->tab.d_tdims,
+                       b->tab.d_tabs, b->tab_stride, b->sm.d_blk_sm, b->nblk_sm, base, n, g.nsplit, S, E, b->Epad, b->sm.d_loglik_sm, b->tab.d_cold_list,
+                       b->tab.d_cold_n, b->cold_cap, b->tab.d_twins, b->tab.d_tlg0, b->d_consts);
+  } else if (r.tabm)
+    hipLaunchKernelGGL(k_emit_tab<kTabTw>, dim3((unsigned)n), dim3(kTabBlock), 0, r.st, r.d_test, r.d_ref, b->tab.d_tdims, b->tab.d_tabs, b->tab_stride, b->tab.d_seg_t,
+                       b->n_jobs, base, S, (uint32_t)((S + kTabTw - 1) / kTabTw), b->d_loglik, b->tab.d_cold_list, b->tab.d_cold_n, b->cold_cap);
+  else
+    hipLaunchKernelGGL(k_emit_batch, dim3((unsigned)n), dim3(kEmitBlock), 0, r.st, r.d_test, r.d_ref, b->d_consts, b->d_cflags, b->d_seg, b->n_jobs, base,
+                       S, (uint32_t)((S + 63) / 64), b->d_tab_gl, b->d_tab_lg, b->d_loglik, b->d_nerr, reinterpret_cast<int*>(b->d_nerr + 1));
+}
+
+// the emissions of group g on the caller's stream: the pieces the plan cuts them into, then the kernel for the cells they left out
+static int run_group_emissions(const Run& r, size_t g)
+{
+  ed_batch* b = r.b;
+  const int64_t E = b->plan->E, S = b->S;
+  const int j0 = b->group_off[g], j1 = b->group_off[g + 1];
+  const edplan::SegKind kind = seg_kind(r.tabm ? b->emit_mode : 0);
+  const std::vector<int64_t>& segv = seg_of(b, kind);
+  const int64_t blk0 = segv[3 * j0], nblk = r.plain ? segv[3 * j1] - blk0 : 0;
+  if (r.tabm && g > 0) HIP_TRY(hipMemsetAsync(b->tab.d_cold_n, 0, (size_t)(kColdLists + 1) * 4, r.st));   // (group 0: zeroed by k_sample_consts)
+  if (!r.plain && g == 0) { if (int rc = run_model_emissions(r)) return rc; }
+  for (const edplan::Piece& pc : edplan::emit_pieces(kind, g, nblk, b->group_off.size() == 2, b->split_frac, (bool)b->split_ev)) {
+    emit_launch(r, pc.n, blk0 + pc.base);
+    if (pc.record) {
+      HIP_TRY(hipEventRecord(b->split_ev, r.st));
+      b->split_recorded = true;
+    }
+  }
+  if (r.tabm && nblk > 0) {  // the cells outside their sample's tables and the samples without tables (returns at once when there are none)
+    const bool csm = r.cl1 || r.tabsm;       // counts walked sample-major ([S][E]: the caller's, or this mode's transposed copy)
+    hipLaunchKernelGGL(k_tab_cold, dim3(1024), dim3(256), 0, r.st, csm ? (r.cl1 ? r.d_test : b->sm.d_test_sm) : r.d_test, csm ? (r.cl1 ? r.d_ref : b->sm.d_ref_sm) : r.d_ref,
+                       b->d_consts, b->d_cflags, b->tab.d_tdims, b->tab.d_cold_list, b->tab.d_cold_n,
+                       b->cold_cap, b->tab.d_seg_t, j0, j1, S, r.tabsm ? b->sm.d_loglik_sm : b->d_loglik, b->d_nerr, r.tabsm ? (int64_t)1 : 3 * S,
+                       r.tabsm ? b->Epad : S, r.tabsm ? 3 * b->Epad : (int64_t)1, csm ? (int64_t)1 : S, csm ? E : (int64_t)1, b->tab.d_notab, b->d_nerr + 2, r.cl1 ? r.cb : 4);
+  }
+  else if (r.plain && nblk > 0)   // the out-of-domain tasks of this group, if k_emit_batch met any (returns at once otherwise)
+    hipLaunchKernelGGL(k_emit_cold, dim3(512), dim3(256), 0, r.st, r.d_test, r.d_ref, b->d_consts, b->d_seg, j0, j1, S, b->d_loglik,
+                       b->d_nerr, reinterpret_cast<int*>(b->d_nerr + 1));
+  HIP_TRY(hipEventRecord(b->job_ev[g], r.st));
+  return ED_OK;
+}
+
+// the chains of group g on its side stream, behind the group's emissions: forward pass, trace-back, call counts
+static int run_group_chains(const Run& r, size_t g, bool& counts_zeroed)
+{
+  ed_batch* b = r.b;
+  const ed_plan* p = b->plan;
+  const int64_t S = b->S;
+  const int32_t C = p->C;
+  const int j0 = b->group_off[g], j1 = b->group_off[g + 1];
+  hipStream_t side = b->sides[g % b->sides.size()];
+  HIP_TRY(hipStreamWaitEvent(side, b->job_ev[g], 0));
+  if (!counts_zeroed) {   // (g == 0; later groups' trace-backs are ordered after it through their own job events on st)
+    HIP_TRY(hipMemsetAsync(b->d_counts, 0, (size_t)S * std::max<int64_t>(C, 1) * 4, side));
+    HIP_TRY(hipEventRecord(b->zero_ev, side));
+    counts_zeroed = true;
+  } else if (b->sides.size() > 1) {
+    HIP_TRY(hipStreamWaitEvent(side, b->zero_ev, 0));
+  }
+  const dim3 gw((unsigned)((S + 63) / 64), (unsigned)((p->max_words + 3) / 4), (unsigned)(j1 - j0));
+  if (r.tabsm) {
+    // a persistent grid, one wave per SIMD, pulling (chromosome, sample group) items longest chromosome first (edtab.inc)
+    const unsigned n_groups = (unsigned)((S + kVitChains - 1) / kVitChains), n_items = n_groups * (unsigned)(j1 - j0);
+    const unsigned n_waves = std::min<unsigned>(n_items, (unsigned)std::max(1, b->vit_waves));
+    hipLaunchKernelGGL(k_viterbi_sm, dim3(n_waves), dim3(kWave), 0,
+                       side, b->sm.d_loglik_sm, b->Epad, p->d_lt3, p->c0, p->c1, p->d_chrom_off, p->d_tile_off, S, C, b->d_bp,
+                       b->d_last, b->d_job_off, b->d_job_chrom, j0, b->sm.d_vit_queue + 2 * (g % 8), n_groups, n_items);
+  }
+  else
+  hipLaunchKernelGGL(k_viterbi, dim3((unsigned)((S + kVitChains - 1) / kVitChains), (unsigned)(j1 - j0)), dim3(kWave), 0,
+                     side, b->d_loglik, p->d_lt3, p->c0, p->c1, p->d_chrom_off, p->d_tile_off, S, C, b->d_bp,
+                     b->d_last, b->d_job_off, b->d_job_chrom, j0);
+  hipLaunchKernelGGL(k_tb_maps, gw, dim3(256), 0, side, b->d_bp, p->d_chrom_off, p->d_tile_off, S, b->d_job_off,
+                     b->d_job_chrom, j0, b->d_maps);
+  hipLaunchKernelGGL(k_tb_chain, dim3((unsigned)((S + kWave - 1) / kWave), (unsigned)(j1 - j0)), dim3(kWave), 0, side,
+                     p->d_chrom_off, p->d_tile_off, S, b->d_job_off, b->d_job_chrom, j0, b->d_last, b->d_maps, b->d_ent);
+  hipLaunchKernelGGL(k_tb_paths<kEagerPath>, gw, dim3(256), 0, side, b->d_bp, p->d_chrom_off, p->d_tile_off, S, C, b->d_job_off,
+                     b->d_job_chrom, j0, b->d_ent, b->d_ppath, b->d_path, b->d_counts);
+  HIP_TRY(hipEventRecord(b->join_ev[g], side));
+  return ED_OK;
+}
+
+// Emissions are issued group by group (groups of whole chromosomes, longest chromosomes first); when a
+// group's emissions are done its Viterbi chains start on the side stream and run underneath the
+// VALU-bound emissions of the following groups.  Only the last group's (short) chains are exposed.
+static int run_groups(const Run& r)
+{
+  ed_batch* b = r.b;
+  const int64_t E = b->plan->E, S = b->S, cells = E * S;
+  const int32_t C = b->plan->C;
+  if (!b->d_loglik && !r.tabsm) {
+    if (b->d_loglik.alloc((size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
+      return ed_fail(ED_ERR_NOMEM, "ed_batch_run: cannot allocate the likelihood matrix");
+  }
+  // the call counts (atomics of k_tb_paths; empty chromosomes: no calls) are zeroed on the first side stream, after the
+  // first group's emissions: off the caller's stream, where it would stand between two emission launches
+  bool counts_zeroed = false;
+  if (!(b->group_off.size() > 1 && cells > 0)) {
+    HIP_TRY(hipMemsetAsync(b->d_counts, 0, (size_t)S * std::max<int64_t>(C, 1) * 4, r.st));
+    counts_zeroed = true;
+  }
+  for (size_t g = 0; g + 1 < b->group_off.size() && cells > 0; ++g) {
+    if (int rc = run_group_emissions(r, g)) return rc;
+    if (int rc = run_group_chains(r, g, counts_zeroed)) return rc;
+  }
+  return ED_OK;
+}
+
+// the side streams joined, then the call table: call counts -> scan -> call records, on the run's tail stream
+static int run_tail(const Run& r)
+{
+  ed_batch* b = r.b;
+  const ed_plan* p = b->plan;
+  const int64_t S = b->S, cells = p->E * S;
+  const int32_t C = p->C;
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[2], r.st));   // all emissions issued and done on the main stream
+  if (r.async) {   // orders `tail` after everything this run put on the caller's stream, groups or not
+    HIP_TRY(hipEventRecord(b->fork_ev, r.st));
+    HIP_TRY(hipStreamWaitEvent(r.tail, b->fork_ev, 0));
+  }
+  for (size_t g = 0; !b->fused && g + 1 < b->group_off.size() && cells > 0; ++g) HIP_TRY(hipStreamWaitEvent(r.tail, b->join_ev[g], 0));
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[3], r.tail));
+  hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, r.tail, b->d_counts, (C > 0 && cells > 0) ? S * C : 0,
+                     b->d_offsets, b->d_total);
+  if (C > 0 && cells > 0)
+    hipLaunchKernelGGL(k_calls_fill, dim3((unsigned)((S + kWave - 1) / kWave), (unsigned)C), dim3(kWave, kCallSeg), 0, r.tail,
+                       b->d_ppath, p->d_chrom_off, p->d_tile_off, S, C, b->d_offsets, b->d_counts, b->d_calls, b->calls_cap());
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[4], r.tail));
+  if (r.async) HIP_TRY(hipEventRecord(b->done_ev, r.tail));
+  HIP_TRY(hipGetLastError());
+  b->ran = true;
+  b->last_run_async = r.async;
+  b->have_run_times = b->timing;
   return ED_OK;
 }
 
@@ -2623,233 +2816,14 @@ static int batch_prepare(ed_batch* b, const double* d_phi, const double* d_expec
 static int batch_run_impl(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, const double* d_phi,
                           const double* d_expected, double mixture, void* stream_, const EmitModel& em)
 {
-  const int bins = em.bins;
-  const double* d_edges = em.edges;
-  const bool plain = (em.bins == 0 && !em.cov);   // per-sample (phi, expected): k_emit_batch with hoisted constants
-  if (!b || !d_test || !d_ref || !d_phi || !d_expected) return ed_fail(ED_ERR_INVALID, "ed_batch_run: NULL argument");
-  if (!plain && b->fused) return ed_fail(ED_ERR_STATE, "ed_batch_run_bins / _cov: not available in fused mode");
-  const bool tabm = plain && b->emit_mode >= 1 && !b->fused;   // emissions from log-gamma difference tables (edtab.inc)
-  const bool tabsm = tabm && b->emit_mode == 2;                // ... sample-major form: tables in LDS, [S][3][Epad] likelihood matrix
-  b->rows_valid = !tabsm;
-  b->path_valid = kEagerPath && !b->fused;   // the byte path is made when it is asked for (ensure_path)
-  const bool cl1 = b->counts_layout == 1;                       // counts handed over sample-major [S][E]
-  if (cl1 && !tabsm) return ed_fail(ED_ERR_STATE, "ed_batch_run: sample-major counts (ed_batch_set_counts_layout(batch, 1)) are served by emit mode 2 only");
-  if (b->counts_bits == 16 && !(cl1 && tabsm)) return ed_fail(ED_ERR_STATE, "ed_batch_run: 16-bit counts (ed_batch_set_counts_bits(batch, 16)) are served by counts_layout 1 + emit mode 2 only");
-  const int cb = b->cb();
-  HIP_TRY(hipSetDevice(b->plan->device));   // the caller's thread may have another device current (one process, many GPUs)
-  hipStream_t st = (hipStream_t)stream_;
-  const ed_plan* p = b->plan;
-  const int64_t E = p->E, S = b->S;
-  const int32_t C = p->C;
-  const bool async = b->async_tail && !b->fused;
-  hipStream_t tail = async ? b->fin : st;   // where the call table is built and the results become available
-  if (b->timing) { if (int rc = fold_run_times(b)) return rc; }
-  // the previous run's asynchronous tail still reads the buffers -- whatever the mode of THIS run (ADVICE r2)
-  if (b->ran && b->last_run_async && b->done_ev) HIP_TRY(hipStreamWaitEvent(st, b->done_ev, 0));
-  b->stream = tail;
-  b->split_recorded = false;
-  b->last_test = d_test; b->last_ref = d_ref; b->last_expected = d_expected; b->last_layout = b->counts_layout; b->last_cb = cb;
+  Run r;
+  if (int rc = run_open(r, b, d_test, d_ref, d_phi, d_expected, mixture, stream_, em)) return rc;
   struct SrcClear { ed_batch* b; ~SrcClear() { b->src_phi = b->src_exp = nullptr; } } src_clear{b};   // (whatever path the run takes)
-  b->last_cov_X = em.cov ? em.X : nullptr; b->last_cov_K = em.cov ? em.K : -1; b->last_cov_beta = em.cov ? em.beta : nullptr;
-  // (the preparation is made by the same submission right before this run -- b->prepared is cleared below -- so a caller that rewrites the
-  // per-sample mixtures behind the same pointer between two runs always gets fresh constants)
-  const bool ready = plain && b->prepared && b->prepared_phi == d_phi && b->prepared_exp == d_expected && b->prepared_mix == mixture &&
-                     b->prepared_mix_s == b->d_mix && !b->fused;
-  b->prepared = false;
-  if (!plain || (ready && !b->prepared_zeroed)) HIP_TRY(hipMemsetAsync(b->d_nerr, 0, 64, st));     // (otherwise: k_sample_consts, below or in batch_prepare)
-  b->prepared_zeroed = false;
-  if (b->timing) HIP_TRY(hipEventRecord(b->ev[0], st));
-  if (plain && !ready) {
-    if (tabm) { if (int rc = tab_setup(b)) return rc; }
-    const bool from_src = b->src_phi && b->src_exp;
-    hipLaunchKernelGGL(k_sample_consts, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, from_src ? b->src_phi : d_phi, from_src ? b->src_exp : d_expected, mixture, S,
-                       b->d_consts, b->d_cflags, b->d_nerr, tabm ? b->tab.d_tacc : (unsigned long long*)nullptr, tabm ? b->tab.d_notab : (unsigned int*)nullptr,
-                       tabm ? b->tab.d_cold_n : (unsigned int*)nullptr, kColdLists + 1,
-                       from_src ? const_cast<double*>(d_phi) : (double*)nullptr, from_src ? const_cast<double*>(d_expected) : (double*)nullptr, b->d_mix);
-    if (tabm) { if (int rc = tab_build(b, d_test, d_ref, st)) return rc; }
-    else if (!b->fused)
-      hipLaunchKernelGGL(k_emit_tables, dim3((unsigned)((S + 63) / 64), (unsigned)(kEmitTab / 4), 3), dim3(256), 0, st, b->d_consts, S,
-                         b->d_tab_gl, b->d_tab_lg);
-  }
-  // one emission launch over workgroups [base, base + n) of the mode's numbering
-  if (tabsm) { if (int rc = tab_setup_sm(b)) return rc; }
-  if (tabsm && E > 0 && !cl1) {   // the counts sample-major (R's own layout; with ed_batch_set_counts_layout(batch, 1) they arrive that way)
-    const dim3 tg((unsigned)((E + 63) / 64), (unsigned)((S + 63) / 64));
-    hipLaunchKernelGGL(k_tab_rows_to_cols, tg, dim3(256), 0, st, d_test, E, S, b->sm.d_test_sm);
-    hipLaunchKernelGGL(k_tab_rows_to_cols, tg, dim3(256), 0, st, d_ref, E, S, b->sm.d_ref_sm);
-  }
-  const std::vector<int64_t>& segv = tabsm ? b->seg_sm : (tabm ? b->seg_t : b->seg);
-  int* const cold_flag = reinterpret_cast<int*>(b->d_nerr + 1);
-  auto emit_launch = [&](int64_t n, int64_t base) {
-    if (n <= 0) return;
-    if (!tabm) {
-      hipLaunchKernelGGL(k_emit_batch, dim3((unsigned)n), dim3(kEmitBlock), 0, st, d_test, d_ref, b->d_consts, b->d_cflags, b->d_seg, b->n_jobs, base,
-                         S, (uint32_t)((S + 63) / 64), b->d_tab_gl, b->d_tab_lg, b->d_loglik, b->d_nerr, cold_flag);
-      return;
-    }
-    if (tabsm) {    // n, base: blocks of 64 exons; every sample gets nsplit workgroups that share them
-      int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(16, (512 + S - 1) / S));
-      nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(nsplit, n / 32));
-      const int64_t nwg = ((S + 7) / 8) * 8 * nsplit;
-      if (cl1 && cb == 2)
-        hipLaunchKernelGGL(k_emit_tab_sm<2>, dim3((unsigned)nwg), dim3(kSmBlock), 0, st, d_test, d_ref, b->tab.d_tdims, b->tab.d_tabs, b->tab_stride,
-                           b->sm.d_blk_sm, b->nblk_sm, base, n, nsplit, S, E, b->Epad, b->sm.d_loglik_sm, b->tab.d_cold_list, b->tab.d_cold_n, b->cold_cap, b->tab.d_twins, b->tab.d_tlg0,
-                           b->d_consts);
-      else
-        hipLaunchKernelGGL(k_emit_tab_sm<4>, dim3((unsigned)nwg), dim3(kSmBlock), 0, st, cl1 ? d_test : b->sm.d_test_sm, cl1 ? d_ref : b->sm.d_ref_sm, b->tab.d_tdims, b->tab.d_tabs, b->tab_stride,
-                           b->sm.d_blk_sm, b->nblk_sm, base, n, nsplit, S, E, b->Epad, b->sm.d_loglik_sm, b->tab.d_cold_list, b->tab.d_cold_n, b->cold_cap, b->tab.d_twins, b->tab.d_tlg0,
-                           b->d_consts);
-      return;
-    }
-    hipLaunchKernelGGL(k_emit_tab<kTabTw>, dim3((unsigned)n), dim3(kTabBlock), 0, st, d_test, d_ref, b->tab.d_tdims, b->tab.d_tabs, b->tab_stride, b->tab.d_seg_t,
-                       b->n_jobs, base, S, (uint32_t)((S + kTabTw - 1) / kTabTw), b->d_loglik, b->tab.d_cold_list, b->tab.d_cold_n, b->cold_cap);
-  };
-  if (b->timing) HIP_TRY(hipEventRecord(b->ev[1], st));
-  const int64_t cells = E * S;
-  if (b->fused) {
-    // One fused launch: every workgroup owns 16 samples x one chromosome (longest chromosomes first) and runs
-    // emissions and Viterbi together (edfused.inc); the likelihood matrix is written only if it is kept.
-    HIP_TRY(hipMemsetAsync(b->d_counts, 0, (size_t)S * std::max<int64_t>(C, 1) * 4, st));   // empty chromosomes: no calls
-    if (b->keep_loglik && !b->d_loglik) {
-      if (b->d_loglik.alloc((size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
-        return ed_fail(ED_ERR_NOMEM, "ed_batch_run: cannot allocate the likelihood matrix (%lld bytes)", (long long)(E * 3 * S * 8));
-    }
-    if (cells > 0 && b->n_jobs > 0)
-      hipLaunchKernelGGL(k_emit_viterbi, dim3((unsigned)((S + kFuS - 1) / kFuS), (unsigned)b->n_jobs), dim3(kFuBlock), 0, st,
-                         d_test, d_ref, b->d_consts, b->d_cflags, p->d_lt3, p->c0, p->c1, p->d_chrom_off, p->d_tile_off, S, C,
-                         b->keep_loglik ? b->d_loglik : (double*)nullptr, b->d_bp, b->d_ppath, b->d_counts, b->d_job_off,
-                         b->d_job_chrom, b->d_nerr);
-    if (b->timing) HIP_TRY(hipEventRecord(b->ev[2], st));
-  } else {
-    if (!b->d_loglik && !tabsm) {
-      if (b->d_loglik.alloc((size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess)
-        return ed_fail(ED_ERR_NOMEM, "ed_batch_run: cannot allocate the likelihood matrix");
-    }
-    // Emissions are issued group by group (groups of whole chromosomes, longest chromosomes first); when a
-    // group's emissions are done its Viterbi chains start on the side stream and run underneath the
-    // VALU-bound emissions of the following groups.  Only the last group's (short) chains are exposed.
-    // the call counts (atomics of k_tb_paths; empty chromosomes: no calls) are zeroed on the first side stream, after the
-    // first group's emissions: off the caller's stream, where it would stand between two emission launches
-    bool counts_zeroed = false;
-    if (!(b->group_off.size() > 1 && cells > 0)) {
-      HIP_TRY(hipMemsetAsync(b->d_counts, 0, (size_t)S * std::max<int64_t>(C, 1) * 4, st));
-      counts_zeroed = true;
-    }
-    for (size_t g = 0; g + 1 < b->group_off.size() && cells > 0; ++g) {
-      const int j0 = b->group_off[g], j1 = b->group_off[g + 1];
-      // One launch per group, except that a group following another starts with a short separate launch: the
-      // previous group's Viterbi workgroups (side stream) are dispatched into the slots freed at that launch
-      // boundary instead of queueing behind this group's thousands of pending workgroups.
-      const int64_t blk0 = segv[3 * j0], nblk = plain ? segv[3 * j1] - blk0 : 0;
-      if (tabm && g > 0) HIP_TRY(hipMemsetAsync(b->tab.d_cold_n, 0, (size_t)(kColdLists + 1) * 4, st));   // (group 0: zeroed by k_sample_consts)
-      const int64_t head = tabsm ? ((g > 0 && nblk > 512) ? 128 : 0) : ((g > 0 && nblk > 2 * kEmitHeadBlocks) ? kEmitHeadBlocks : 0);
-      if (!plain && g == 0)   // one launch over every cell; the Viterbi groups follow it
-      {
-        const int64_t eblk = (E + kEmitBlock / 64 - 1) / (kEmitBlock / 64);   // 4 exons x 64 samples per workgroup
-        const dim3 egrid((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(eblk, 65535), (unsigned)((eblk + 65534) / 65535));
-        const double* ctab = nullptr;
-        if (bins > 0 && !em.cov) {
-          // depth-binned dispersion: the constants lbeta(a1, a2) per (sample, state, reference count) first, then three tasks per cell
-          if (int rc = bins_ctab_setup(b, (size_t)egrid.x * egrid.y * egrid.z)) return rc;
-          hipLaunchKernelGGL(k_bins_ctab, dim3((unsigned)((S + 63) / 64), (unsigned)(kBinsRtab / 4)), dim3(256), 0, st, bins, d_edges, d_phi, d_expected,
-                             mixture, S, kBinsRtab, b->ctab.d_ctab, em.skip, b->d_mix);
-          // In the cohort pipeline the launch is cut into pieces: the NEXT slab's fit consists of several kernels whose workgroups need a
-          // (nearly) whole CU each, and such a workgroup only gets one at a launch boundary, where the CUs drain -- under one uncut
-          // launch the 3.5-ms fit took the launch's whole 13.8 ms and then stood between two emission launches.
-          const int pieces = (int)std::max<int64_t>(1, std::min<int64_t>(b->bins_pieces, eblk));
-          for (int pc = 0; pc < pieces; ++pc) {
-            const int64_t pb0 = eblk * pc / pieces, pb1 = eblk * (pc + 1) / pieces, pn = pb1 - pb0;
-            if (pn <= 0) continue;
-            const dim3 pgrid((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(pn, 65535), (unsigned)((pn + 65534) / 65535));
-            hipLaunchKernelGGL(k_emit_bins_tab, pgrid, dim3(kEmitBlock), 0, st, d_test, d_ref, bins, d_edges, d_phi, d_expected, mixture, E, S,
-                               b->ctab.d_ctab, kBinsRtab, b->d_loglik, b->ctab.d_left_out, em.skip, pb0, pn, b->d_mix);
-          }
-          ctab = b->ctab.d_ctab;
-        }
-        {
-          const int tpw = ctab ? 32 : 1;   // behind the tabulated kernel nearly every tile returns on one byte (1 / 8 / 32 on one box: 17.0 / 16.2 / 16.1 ms per slab)
-          const int64_t nwg = (eblk + tpw - 1) / tpw;
-          const dim3 fgrid((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(nwg, 65535), (unsigned)((nwg + 65534) / 65535));
-          hipLaunchKernelGGL(k_emit_bins, fgrid,
-                             dim3(kEmitBlock), 0, st, d_test, d_ref, bins, d_edges, d_phi, em.cov ? (const double*)nullptr : d_expected, em.X,
-                             em.cov ? em.K : -1, em.beta, mixture, E, S, b->d_loglik,
-                             b->d_nerr, ctab, kBinsRtab, b->ctab.d_left_out, em.skip, tpw, eblk, b->d_mix);
-        }
-      }
-      emit_launch(head, blk0);
-      // single-group mode with a split: [first part][split_ev][rest]; the cut is a multiple of 8 workgroups (XCD numbering)
-      int64_t cut = 0;
-      if (plain && b->group_off.size() == 2 && b->split_frac > 0.0 && b->split_frac < 1.0 && b->split_ev) {
-        cut = ((int64_t)((double)nblk * b->split_frac) / 8) * 8;     // (mode 2: blocks of 64 exons -- any cut will do)
-        if (cut <= 0 || cut >= nblk) cut = 0;
-      }
-      if (cut > 0) {
-        emit_launch(cut, blk0);
-        HIP_TRY(hipEventRecord(b->split_ev, st));
-        b->split_recorded = true;
-      }
-      emit_launch(nblk - head - cut, blk0 + head + cut);
-      if (tabm && nblk > 0) {  // the cells outside their sample's tables and the samples without tables (returns at once when there are none)
-        const bool csm = cl1 || tabsm;       // counts walked sample-major ([S][E]: the caller's, or this mode's transposed copy)
-        hipLaunchKernelGGL(k_tab_cold, dim3(1024), dim3(256), 0, st, csm ? (cl1 ? d_test : b->sm.d_test_sm) : d_test, csm ? (cl1 ? d_ref : b->sm.d_ref_sm) : d_ref,
-                           b->d_consts, b->d_cflags, b->tab.d_tdims, b->tab.d_cold_list, b->tab.d_cold_n,
-                           b->cold_cap, b->tab.d_seg_t, j0, j1, S, tabsm ? b->sm.d_loglik_sm : b->d_loglik, b->d_nerr, tabsm ? (int64_t)1 : 3 * S,
-                           tabsm ? b->Epad : S, tabsm ? 3 * b->Epad : (int64_t)1, csm ? (int64_t)1 : S, csm ? E : (int64_t)1, b->tab.d_notab, b->d_nerr + 2, cl1 ? cb : 4);
-      }
-      else if (plain && nblk > 0)   // the out-of-domain tasks of this group, if k_emit_batch met any (returns at once otherwise)
-        hipLaunchKernelGGL(k_emit_cold, dim3(512), dim3(256), 0, st, d_test, d_ref, b->d_consts, b->d_seg, j0, j1, S, b->d_loglik,
-                           b->d_nerr, cold_flag);
-      HIP_TRY(hipEventRecord(b->job_ev[g], st));
-      hipStream_t side = b->sides[g % b->sides.size()];
-      HIP_TRY(hipStreamWaitEvent(side, b->job_ev[g], 0));
-      if (!counts_zeroed) {   // (g == 0; later groups' trace-backs are ordered after it through their own job events on st)
-        HIP_TRY(hipMemsetAsync(b->d_counts, 0, (size_t)S * std::max<int64_t>(C, 1) * 4, side));
-        HIP_TRY(hipEventRecord(b->zero_ev, side));
-        counts_zeroed = true;
-      } else if (b->sides.size() > 1) {
-        HIP_TRY(hipStreamWaitEvent(side, b->zero_ev, 0));
-      }
-      const dim3 gw((unsigned)((S + 63) / 64), (unsigned)((p->max_words + 3) / 4), (unsigned)(j1 - j0));
-      if (tabsm) {
-        // a persistent grid, one wave per SIMD, pulling (chromosome, sample group) items longest chromosome first (edtab.inc)
-        const unsigned n_groups = (unsigned)((S + kVitChains - 1) / kVitChains), n_items = n_groups * (unsigned)(j1 - j0);
-        const unsigned n_waves = std::min<unsigned>(n_items, (unsigned)std::max(1, b->vit_waves));
-        hipLaunchKernelGGL(k_viterbi_sm, dim3(n_waves), dim3(kWave), 0,
-                           side, b->sm.d_loglik_sm, b->Epad, p->d_lt3, p->c0, p->c1, p->d_chrom_off, p->d_tile_off, S, C, b->d_bp,
-                           b->d_last, b->d_job_off, b->d_job_chrom, j0, b->sm.d_vit_queue + 2 * (g % 8), n_groups, n_items);
-      }
-      else
-      hipLaunchKernelGGL(k_viterbi, dim3((unsigned)((S + kVitChains - 1) / kVitChains), (unsigned)(j1 - j0)), dim3(kWave), 0,
-                         side, b->d_loglik, p->d_lt3, p->c0, p->c1, p->d_chrom_off, p->d_tile_off, S, C, b->d_bp,
-                         b->d_last, b->d_job_off, b->d_job_chrom, j0);
-      hipLaunchKernelGGL(k_tb_maps, gw, dim3(256), 0, side, b->d_bp, p->d_chrom_off, p->d_tile_off, S, b->d_job_off,
-                         b->d_job_chrom, j0, b->d_maps);
-      hipLaunchKernelGGL(k_tb_chain, dim3((unsigned)((S + kWave - 1) / kWave), (unsigned)(j1 - j0)), dim3(kWave), 0, side,
-                         p->d_chrom_off, p->d_tile_off, S, b->d_job_off, b->d_job_chrom, j0, b->d_last, b->d_maps, b->d_ent);
-      hipLaunchKernelGGL(k_tb_paths<kEagerPath>, gw, dim3(256), 0, side, b->d_bp, p->d_chrom_off, p->d_tile_off, S, C, b->d_job_off,
-                         b->d_job_chrom, j0, b->d_ent, b->d_ppath, b->d_path, b->d_counts);
-      HIP_TRY(hipEventRecord(b->join_ev[g], side));
-    }
-    if (b->timing) HIP_TRY(hipEventRecord(b->ev[2], st));   // all emissions issued and done on the main stream
-    if (async) {   // orders `tail` after everything this run put on the caller's stream, groups or not
-      HIP_TRY(hipEventRecord(b->fork_ev, st));
-      HIP_TRY(hipStreamWaitEvent(tail, b->fork_ev, 0));
-    }
-    for (size_t g = 0; g + 1 < b->group_off.size() && cells > 0; ++g) HIP_TRY(hipStreamWaitEvent(tail, b->join_ev[g], 0));
-  }
-  if (b->timing) HIP_TRY(hipEventRecord(b->ev[3], tail));
-  hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, tail, b->d_counts, (C > 0 && cells > 0) ? S * C : 0,
-                     b->d_offsets, b->d_total);
-  if (C > 0 && cells > 0)
-    hipLaunchKernelGGL(k_calls_fill, dim3((unsigned)((S + kWave - 1) / kWave), (unsigned)C), dim3(kWave, kCallSeg), 0, tail,
-                       b->d_ppath, p->d_chrom_off, p->d_tile_off, S, C, b->d_offsets, b->d_counts, b->d_calls, b->calls_cap());
-  if (b->timing) HIP_TRY(hipEventRecord(b->ev[4], tail));
-  if (async) HIP_TRY(hipEventRecord(b->done_ev, tail));
-  HIP_TRY(hipGetLastError());
-  b->ran = true;
-  b->last_run_async = async;
-  b->have_run_times = b->timing;
-  return ED_OK;
+  if (int rc = run_consts(r)) return rc;
+  if (int rc = run_transpose(r)) return rc;
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[1], r.st));
+  if (int rc = b->fused ? run_fused(r) : run_groups(r)) return rc;
+  return run_tail(r);
 }
 
 ED_EXPORT int ed_batch_run(ed_batch* b, const int32_t* d_test, const int32_t* d_ref, const double* d_phi,
@@ -3212,15 +3186,8 @@ ED_EXPORT int ed_batch_n_emit_launches(const ed_batch* b)
 try {
   if (!b) return 0;
   if (b->fused) return 1;
-  int n = 0;
-  for (size_t g = 0; g + 1 < b->group_off.size(); ++g) {
-    const std::vector<int64_t>& segv = (b->emit_mode == 2 && !b->seg_sm.empty()) ? b->seg_sm : ((b->emit_mode == 1 && !b->seg_t.empty()) ? b->seg_t : b->seg);
-    const int64_t nblk = segv[3 * b->group_off[g + 1]] - segv[3 * b->group_off[g]];
-    const int64_t head = b->emit_mode == 2 ? ((g > 0 && nblk > 512) ? 128 : 0) : ((g > 0 && nblk > 2 * kEmitHeadBlocks) ? kEmitHeadBlocks : 0);
-    n += (head > 0) + (nblk - head > 0);
-  }
-  if (b->group_off.size() == 2 && b->split_frac > 0.0 && b->split_frac < 1.0 && b->split_ev) n += 1;
-  return n;
+  const edplan::SegKind kind = seg_kind(b->emit_mode);   // (what a run of the per-sample model issues with the batch's settings as they are)
+  return edplan::n_emit_launches(kind, seg_of(b, kind), b->group_off, b->split_frac, (bool)b->split_ev);
 }
 ED_CATCH("ed_batch_n_emit_launches")
 

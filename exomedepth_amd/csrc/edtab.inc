@@ -39,7 +39,6 @@ constexpr int kTabBlock = 256;
 // wave picks its list from its workgroup number): one counter for the whole launch was the same-address atomic of ~5e5 waves per slab.
 // cold_n[kColdLists] is raised when a list ran out: the strict pass then looks at every cell of the launch again.
 constexpr int kColdLists = 1024;
-constexpr uint32_t kTabRun = 256;      // exon blocks an XCD spends on one sample block before taking up the next
 
 // per-sample sums over a sample of the exons -- every `step`-th piece of 64 consecutive exons (so that the sample-major form below
 // reads whole 256-byte pieces and both forms look at the SAME exons: the table lengths, hence which cells take the strict
@@ -415,7 +414,6 @@ typedef unsigned int ed_v2u __attribute__((ext_vector_type(2)));
 // blocks x, x + 8, ... ONE at a time, as k_emit_batch does): 16 samples x ~0.3 MB of hot entries.  Counts and likelihood
 // rows are streamed with nontemporal hints so that they do not evict the tables.  Same segment / launch-range interface as
 // k_emit_batch (seg built for this tile shape: ed_batch::seg_t).  Launched with TW = kTabTw.
-constexpr int kTabTw = 16;
 template <int TW>
 __global__ void __launch_bounds__(kTabBlock)
 k_emit_tab(const int32_t* __restrict__ test, const int32_t* __restrict__ ref, const int4* __restrict__ dims,

@@ -231,8 +231,9 @@ int ed_batch_set_mixture(ed_batch* batch, const double* d_mixture);
  * ed_batch_copy_loglik() fails with ED_ERR_STATE, 3*8*n_exons*n_samples bytes of HBM are not allocated. */
 int ed_batch_set_fused(ed_batch* batch, int fused);
 int ed_batch_keep_loglik(ed_batch* batch, int keep);
-/* Number of emission-kernel launches one ed_batch_run issues (= overlap groups; 1 in fused mode): the
- * denominator of per-launch figures in bench.py. */
+/* Number of emission-kernel launches one ed_batch_run issues with the batch's settings as they are: per overlap group one
+ * launch, plus a short leading launch for a long group that follows another, plus one where a single group is split
+ * (csrc/ed_launch_plan.hpp: emit_pieces); 1 in fused mode.  The denominator of per-launch figures in bench.py. */
 int ed_batch_n_emit_launches(const ed_batch* batch);
 
 /* Pipelining consecutive batches.  By default ed_batch_run joins everything it started back into `stream`: the stream is

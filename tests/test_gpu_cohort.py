@@ -439,3 +439,46 @@ def test_test_counts_from_the_host_references_on_the_device(cohort_data):
             _same(co.results(tickets[i - 1], slabs[i - 1][0].shape[1], path=True), want[i - 1], ("calls", "info", "path", "phi", "expected"))
     _same(co.results(tickets[-1], slabs[-1][0].shape[1], path=True), want[-1], ("calls", "info", "path", "phi", "expected"))
     co.close()
+
+
+def _blocks_of_64(sizes):
+    """blocks of 64 exons on the absolute exon grid, clipped to their chromosome (csrc/ed_launch_plan.hpp: segments, sample-major kind)"""
+    off = np.concatenate(([0], np.cumsum(sizes)))
+    return int(sum(-(-int(hi) // 64) - int(lo) // 64 for lo, hi in zip(off[:-1], off[1:])))
+
+
+# strict mode, 3 samples: tiles of 4 exons x 64 samples, one sample block -> 15 + 10 = 25 and 18 + 12 = 30 workgroups; mode 2: blocks of 64 exons.
+# The cut of a single group's emissions is floor(n * 0.3) rounded down to a multiple of 8: 25, 26 -> 7 -> no cut, ONE launch; 30 -> 9 -> cut at 8.
+@pytest.mark.parametrize("emit_mode,sizes,units,launches", [(0, (60, 40), 25, 1), (0, (72, 48), 30, 2), (2, (1000, 600), 26, 1), (2, (1000, 856), 30, 2)])
+def test_a_split_that_rounds_to_nothing_is_one_launch(edlib, emit_mode, sizes, units, launches):
+    """Pipelined cohort, one overlap group, option split = 0.3: where the cut rounds to zero workgroups the run issues one emission launch and
+    records no split event, and n_emit_launches says what the run issues; the results are the batch interface's bits either way."""
+    if emit_mode == 2:
+        assert _blocks_of_64(sizes) == units
+    else:
+        assert sum(-(-m // 4) for m in sizes) == units
+    from exomedepth_amd import synth
+    chrom_off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int32)
+    start = np.concatenate([1000 + 3000 * np.arange(m) for m in sizes]).astype(np.int32)
+    plan = edlib.Plan(chrom_off, start, start + 200)
+    n = 3
+    slabs = []
+    for k in range(3):
+        test, ref, _, _, _ = synth.counts_numpy(chrom_off, n, seed=900 + k, n_segments=2, mean_depth=80.0)
+        slabs.append((test, ref))
+    want = _reference_results(edlib, plan, slabs, emit_mode)
+    co = edlib.Cohort(plan, n, 2, viterbi_overlap=0, split=0.3, emit_mode=emit_mode)
+    assert co.n_emit_launches == launches
+    dev = [(edlib.DeviceArray(t), edlib.DeviceArray(r)) for t, r in slabs]
+    tickets = []
+    for rounds in range(2):                                        # every slot is reused while its predecessor is in flight
+        for i, (dt, dr) in enumerate(dev):
+            if len(tickets) >= 2:
+                j = len(tickets) - 2
+                _same(co.results(tickets[j], n, path=True, loglik=True), want[j % 3], ("calls", "info", "path", "loglik", "phi", "expected"))
+            tickets.append(co.submit(dt, dr, n_samples=n))
+    for j in range(len(tickets) - 2, len(tickets)):
+        _same(co.results(tickets[j], n, path=True, loglik=True), want[j % 3], ("calls", "info", "path", "loglik", "phi", "expected"))
+    assert co.n_emit_launches == launches
+    co.close()
+    plan.close()
