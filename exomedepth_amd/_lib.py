@@ -181,6 +181,14 @@ SYMBOLS = [
     ("ed_readcount_kernel_ms", C.c_int, [_vp, C.POINTER(_dbl), C.POINTER(_dbl)]),
     ("ed_readcount_geometry", C.c_int, [C.POINTER(_i32)]),
     ("ed_bam_scan_records", C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    ("ed_plan_posterior", C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    ("ed_plan_call_posterior", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    ("ed_batch_copy_posterior", C.c_int, [_vp, _vp]),
+    ("ed_batch_posterior", _vp, [_vp]),
+    ("ed_batch_copy_log_evidence", C.c_int, [_vp, _vp]),
+    ("ed_batch_copy_call_posterior", C.c_int, [_vp, _vp, _i64]),
+    ("ed_batch_n_posterior_passes", _i64, [_vp]),
+    ("ed_batch_posterior_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
 ]
 
 

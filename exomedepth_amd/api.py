@@ -29,6 +29,7 @@ assert CALL_DTYPE.itemsize == C.sizeof(EdCall)
 CALL_INFO_DTYPE = np.dtype([("BF_raw", "<f8"), ("BF", "<f8"), ("reads_expected", "<i8"), ("reads_observed", "<i8"),
                             ("reads_ratio", "<f8")])
 assert CALL_INFO_DTYPE.itemsize == C.sizeof(EdCallInfo)
+CALL_POST_DTYPE = np.dtype([("post_mean", "<f8"), ("post_min", "<f8"), ("log_p_all", "<f8"), ("log_evidence", "<f8")])
 
 
 def _ptr(a):
@@ -212,6 +213,11 @@ class Plan:
                                    _ptr(self.start), _ptr(self.end), self.transition_probability,
                                    self.expected_CNV_length))
 
+    def posterior(self, loglik, n_samples, stream=None):
+        """Forward-backward on a likelihood matrix (n_exons, 3, n_samples) -- columns deletion, normal, duplication; host data, a
+        DeviceArray or a torch device tensor: the caller's own emissions are as good as a batch's.  Returns a Posterior."""
+        return Posterior(self, loglik, int(n_samples), stream)
+
     def close(self):
         if self.handle:
             lib().ed_plan_destroy(self.handle)
@@ -222,6 +228,57 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+class Posterior:
+    """Device-resident result of Plan.posterior: the backward messages, the log posterior of deletion / duplication per exon and the
+    log-evidence of every (sample, chromosome) chain (include/exomedepth_amd.h: ed_plan_posterior)."""
+
+    def __init__(self, plan, loglik, n_samples, stream=None):
+        self.plan, self.n_samples, self.stream = plan, n_samples, stream
+        E, Cn, S = plan.n_exons, plan.n_chrom, n_samples
+        if not _is_device(loglik) and np.shape(loglik) != (E, 3, S):
+            raise ValueError("loglik must have shape (%d, 3, %d), got %s" % (E, S, np.shape(loglik)))
+        self._keep = []
+        self._ll = _device_pointer(loglik, np.float64, self._keep)
+        if _is_device(loglik):
+            self._keep.append(loglik)
+        self._work = DeviceArray(nbytes=E * 3 * S * 8)
+        self._logpost = DeviceArray(nbytes=E * 2 * S * 8)
+        self._logev = DeviceArray(nbytes=Cn * S * 8)
+        check(lib().ed_plan_posterior(plan.handle, self._ll, S, self._work.ptr, self._logpost.ptr, self._logev.ptr, stream))
+        check(lib().ed_synchronize(stream))
+
+    def log_posterior(self):
+        """(n_exons, 2, n_samples): [:,0,:] deletion, [:,1,:] duplication"""
+        return self._logpost.to_host(np.float64, (self.plan.n_exons, 2, self.n_samples))
+
+    def posterior(self):
+        return np.exp(self.log_posterior())
+
+    def log_evidence(self):
+        """(n_chrom, n_samples)"""
+        return self._logev.to_host(np.float64, (self.plan.n_chrom, self.n_samples))
+
+    def beta(self):
+        """(n_exons, 3, n_samples) backward log-messages, rows in HMM state order: normal, deletion, duplication"""
+        return self._work.to_host(np.float64, (self.plan.n_exons, 3, self.n_samples))
+
+    def device_pointers(self):
+        return {"work": self._work.ptr.value, "logpost": self._logpost.ptr.value, "log_evidence": self._logev.ptr.value}
+
+    def call_posterior(self, calls):
+        """post_mean, post_min, log_p_all, log_evidence of call rows (a CALL_DTYPE array)"""
+        calls = np.ascontiguousarray(calls, dtype=CALL_DTYPE)
+        out = np.zeros(calls.size, dtype=CALL_POST_DTYPE)
+        check(lib().ed_plan_call_posterior(self.plan.handle, _ptr(calls), calls.size, self._ll, self.n_samples, self._work.ptr,
+                                           self._logpost.ptr, self._logev.ptr, _ptr(out), self.stream))
+        return out
+
+    def free(self):
+        for d in (self._work, self._logpost, self._logev):
+            d.free()
+        self._keep = []
 
 
 class Batch:
@@ -461,6 +518,36 @@ class Batch:
         out = np.empty((self.plan.n_exons, self.n_samples), dtype=np.uint8)
         check(lib().ed_batch_copy_path(self.handle, _ptr(out)))
         return out
+
+    def posterior(self, log=False):
+        """(n_exons, 2, n_samples): posterior probability of [:,0,:] deletion and [:,1,:] duplication at every exon of the last run
+        (log=True: its logarithm, as the device holds it).  Forward-backward on the run's likelihood matrix, made on the first request."""
+        out = np.empty((self.plan.n_exons, 2, self.n_samples), dtype=np.float64)
+        check(lib().ed_batch_copy_posterior(self.handle, _ptr(out)))
+        return out if log else np.exp(out)
+
+    def log_evidence(self):
+        """(n_chrom, n_samples): log-probability of every chain's observations under the HMM (0 for an empty chromosome)"""
+        out = np.empty((self.plan.n_chrom, self.n_samples), dtype=np.float64)
+        check(lib().ed_batch_copy_log_evidence(self.handle, _ptr(out)))
+        return out
+
+    def call_posterior(self):
+        """post_mean, post_min, log_p_all, log_evidence of every call (row i belongs to row i of calls())"""
+        n = self.n_calls()
+        out = np.zeros(n, dtype=CALL_POST_DTYPE)
+        check(lib().ed_batch_copy_call_posterior(self.handle, _ptr(out), n))
+        return out
+
+    def posterior_ms(self):
+        """with enable_timing(): dict(backward, forward, call_post) in ms of the last run's posterior request (0: not timed)"""
+        ms = (C.c_float * 3)()
+        check(lib().ed_batch_posterior_ms(self.handle, ms))
+        return dict(zip(("backward", "forward", "call_post"), (float(x) for x in ms)))
+
+    def n_posterior_passes(self):
+        """times the forward-backward passes have been enqueued on this batch (a second request after a run launches nothing)"""
+        return int(lib().ed_batch_n_posterior_passes(self.handle))
 
     def loglik(self):
         """(n_exons, 3, n_samples): [:,0,:] deletion, [:,1,:] normal, [:,2,:] duplication."""
@@ -739,9 +826,10 @@ class Cohort:
         b = Batch._view(self.plan, int(lib().ed_batch_n_samples(h)), h.value)   # the ticket's own width (a short last slab has its own batch)
         return b, pp.value, pe.value
 
-    def results(self, ticket, n_samples, path=False, loglik=False, info=True):
+    def results(self, ticket, n_samples, path=False, loglik=False, info=True, posterior=False):
         """host copies of a ticket's results: dict(calls, info, phi, expected[, path][, loglik]); with the option phi_bins = B > 1
-        phi_bins (B, n) and edges (B + 1, n) stand where phi is"""
+        phi_bins (B, n) and edges (B + 1, n) stand where phi is.  posterior=True adds call_posterior (Batch.call_posterior) and
+        log_evidence; posterior="matrix" also the exon posteriors (Batch.posterior) as `posterior`"""
         b, pp, pe = self.batch(ticket)
         b.n_samples = int(n_samples)
         out = {"calls": b.calls()}
@@ -761,6 +849,11 @@ class Cohort:
             out["path"] = b.path()
         if loglik:
             out["loglik"] = b.loglik()
+        if posterior:
+            out["call_posterior"] = b.call_posterior()
+            out["log_evidence"] = b.log_evidence()
+            if posterior == "matrix":
+                out["posterior"] = b.posterior()
         return out
 
     def wait(self, ticket):
@@ -1017,7 +1110,7 @@ class ExomeDepth:
         col = 0 if type == "deletion" else 2
         return float(np.sum(self.likelihood[which, col] - self.likelihood[which, 1]))
 
-    def CallCNVs(self, chromosome, start, end, name, transition_probability=1e-4, expected_CNV_length=50000):
+    def CallCNVs(self, chromosome, start, end, name, transition_probability=1e-4, expected_CNV_length=50000, posterior=False):
         """reference R/class_definition.R:311-419: order exons, one Viterbi chain per chromosome,
         call table with start.p/end.p (1-based, global), type, nexons, start, end, chromosome, id.
 
@@ -1025,7 +1118,11 @@ class ExomeDepth:
         x@likelihood (:327-336) but not x@expected / x@phi, and then indexes x@expected with the reordered positions
         (:396) -- with a per-exon `expected` (covariates in the formula) its reads.expected is then summed over the wrong
         exons.  Here phi and expected are reordered with everything else, so reads.expected belongs to the call's exons.
-        With the default formula (expected constant) the two agree."""
+        With the default formula (expected constant) the two agree.
+
+        posterior=True adds four columns from the HMM's forward-backward pass (not in the reference): post.mean / post.min, the mean
+        and the smallest posterior probability of the call's type over its exons; post.all, the log-probability that every exon of
+        the call is in that state; log.evidence, the log-evidence of the call's chromosome."""
         if self.phi.size == 0:
             self.CNV_calls = []
             return self
@@ -1058,6 +1155,7 @@ class ExomeDepth:
                           self.phi[:1], self.expected[:1], mixture=self.prop_tumor)
                 raw = batch.calls()
                 self.Viterbi_path = batch.path()[:, 0].astype(np.int64)
+                cpost = batch.call_posterior() if posterior else None
             finally:
                 batch.close()
                 plan.close()
@@ -1079,7 +1177,19 @@ class ExomeDepth:
                 self.Viterbi_path[lo:hi] = res["Viterbi.path"][1:-1]
                 for r in res["calls"]:
                     raw.append({"start_exon": int(r["start.p"]) - 2 + lo, "end_exon": int(r["end.p"]) - 2 + lo,
-                                "type": int(r["type"]), "nexons": int(r["nexons"])})
+                                "type": int(r["type"]), "nexons": int(r["nexons"]), "chrom": c})
+            cpost = None
+            if posterior:
+                rows = np.zeros(len(raw), dtype=CALL_DTYPE)
+                for k in ("chrom", "start_exon", "end_exon", "type", "nexons"):
+                    rows[k] = [r[k] for r in raw]
+                plan = Plan(chrom_off, start, end, transition_probability, expected_CNV_length)
+                try:
+                    post = plan.posterior(np.ascontiguousarray(self.likelihood).reshape(n, 3, 1), 1)
+                    cpost = post.call_posterior(rows)
+                    post.free()
+                finally:
+                    plan.close()
         calls = []
         total = self.test + self.reference
         for r in raw:
@@ -1097,6 +1207,10 @@ class ExomeDepth:
                           "BF": _signif(np.log10(np.e) * bf, 3), "reads.expected": reads_expected,
                           "reads.observed": reads_observed,
                           "reads.ratio": _signif(ratio, 3)})
+            if cpost is not None:
+                q = cpost[len(calls) - 1]
+                calls[-1].update({"post.mean": float(q["post_mean"]), "post.min": float(q["post_min"]),
+                                  "post.all": float(q["log_p_all"]), "log.evidence": float(q["log_evidence"])})
         self.CNV_calls = calls
         return self
 

@@ -1719,6 +1719,12 @@ struct SmSet {       // emit mode 2 (sample-major form): the counts as [S][E], t
   DevBuf<unsigned int> d_vit_queue;    // [8][2] work counters of k_viterbi_sm's persistent grid (one pair per launch group in flight; self-resetting)
   bool made() const { return (bool)d_loglik_sm; }
 };
+struct PostSet {     // forward-backward of the last run (edpost.inc), made on the first request
+  DevBuf<double> d_beta;         // [E][3][S] backward log-messages, HMM state order
+  DevBuf<double> d_logpost;      // [E][2][S] log posterior of deletion, duplication
+  DevBuf<double> d_logev;        // [C][S] log-evidence of every chain
+  bool made() const { return (bool)d_beta; }
+};
 struct CtabSet {     // depth-binned model, tabulated constants (edbins.inc)
   DevBuf<double> d_ctab;         // [3][kBinsRtab][S] lbeta(a1, a2) of the depth-binned model per reference count
   DevBuf<uint8_t> d_left_out;    // one byte per workgroup of k_emit_bins_tab: a cell was left to the per-cell kernel
@@ -1809,6 +1815,12 @@ struct ed_batch {
   int last_cov_K = -1;
   bool ran = false;
   bool path_valid = true;    // d_path holds the byte-per-exon path of the last run; a run clears it, ensure_path makes the path from ppath
+  bool post_valid = false;   // `post` holds the posterior of the last run; a run clears it, ensure_post runs the two passes (edpost.inc)
+  int64_t post_passes = 0;   // times ensure_post has enqueued them
+  PostSet post;
+  DevBuf<ed_call_post> d_cpost;  // per-call posterior summary, grow-only (as d_info)
+  Event post_ev[5];              // with `timing`: around k_fb_backward / k_fb_forward (0..2) and k_call_post (3, 4); made on first use
+  bool post_timed = false, cpost_timed = false;
   bool fused = false;        // run emissions + Viterbi as ONE kernel (edfused.inc) instead of two overlapped ones
   bool keep_loglik = true;   // fused mode only: also write the [E][3][S] likelihood matrix (the S4 `likelihood` slot)
   int fit_hist = 1;          // ed_batch_fit: 1 = iterate on count histograms (one pass over the counts), geometry picked from
@@ -2563,6 +2575,7 @@ static int run_open(Run& r, ed_batch* b, const int32_t* d_test, const int32_t* d
   r.tabsm = r.tabm && b->emit_mode == 2;
   b->rows_valid = !r.tabsm;
   b->path_valid = kEagerPath && !b->fused;   // the byte path is made when it is asked for (ensure_path)
+  b->post_valid = false;                      // ... and so is the posterior (ensure_post)
   r.cl1 = b->counts_layout == 1;
   if (r.cl1 && !r.tabsm) return ed_fail(ED_ERR_STATE, "ed_batch_run: sample-major counts (ed_batch_set_counts_layout(batch, 1)) are served by emit mode 2 only");
   if (b->counts_bits == 16 && !(r.cl1 && r.tabsm)) return ed_fail(ED_ERR_STATE, "ed_batch_run: 16-bit counts (ed_batch_set_counts_bits(batch, 16)) are served by counts_layout 1 + emit mode 2 only");
@@ -3503,4 +3516,5 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edrefcohort.inc"
 #include "edpca.inc"
 #include "edannot.inc"
+#include "edpost.inc"
 #include "edreadcount.inc"

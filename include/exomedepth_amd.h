@@ -280,6 +280,56 @@ int ed_batch_copy_call_info(ed_batch* batch, ed_call_info* host_info, int64_t ca
 int ed_batch_copy_path(ed_batch* batch, uint8_t* host_path /* [n_exons][n_samples] */);
 int ed_batch_copy_loglik(ed_batch* batch, double* host_loglik /* [n_exons][3][n_samples] */);
 
+/* ---- forward-backward: exon posteriors, chain log-evidence, per-call confidence ----
+ * The HMM is the one the Viterbi path is decoded from (states normal / deletion / duplication, the plan's distance-dependent
+ * log-transitions, the chain started in `normal` and closed by the dummy observation whose state is forced to `normal`).  With
+ * alpha / beta the forward / backward log-messages of a (sample, chromosome) chain and logZ its log-evidence (the log-probability
+ * of the chain's observations under the model, all paths summed), the posterior of state j at exon i is
+ *   log gamma_i(j) = alpha_i(j) + beta_i(j) - logZ.
+ * Deterministic: one operation order per chain, no atomics; a sample's values do not depend on its batch-mates or the batch width.
+ * A chain with a NaN emission has NaN log-evidence and unspecified exons; every other chain is unaffected.  A chain no path can
+ * explain (every state -inf at some exon) has log-evidence -inf.  An empty chromosome's log-evidence is 0.
+ *
+ * ed_plan_posterior: the core, on any caller-supplied DEVICE matrix d_loglik [n_exons][3][n_samples] (columns deletion, normal,
+ *   duplication: the layout of ed_batch_loglik).  Enqueues two kernels on `stream` and returns; on their completion
+ *     d_work      [n_exons][3][n_samples]  holds beta, rows in HMM state order (0 normal, 1 deletion, 2 duplication)
+ *     d_logpost   [n_exons][2][n_samples]  log gamma of deletion (row 0) and duplication (row 1)
+ *     d_log_evidence [n_chrom][n_samples]  logZ of every chain
+ *   1 <= n_samples <= 32768.
+ * ed_plan_call_posterior: the summary below for HOST rows `calls` (each inside its chromosome, sample < n_samples, type 1 or 2) from
+ *   the device arrays ed_plan_posterior filled, enqueued on the same stream; waits and writes out[0 .. n_calls). */
+typedef struct {
+  double post_mean;     /* mean over the call's exons of gamma_i(type) */
+  double post_min;      /* ... and the smallest */
+  double log_p_all;     /* log-probability that EVERY exon start_exon .. end_exon is in state `type`, given the chain's data (defined
+                         * for the rows that span mixed states too: a second call that inherited the first one's start) */
+  double log_evidence;  /* logZ of the call's chain */
+} ed_call_post;
+int ed_plan_posterior(const ed_plan* plan, const double* d_loglik, int64_t n_samples, double* d_work, double* d_logpost,
+                      double* d_log_evidence, void* stream);
+int ed_plan_call_posterior(const ed_plan* plan, const ed_call* calls, int64_t n_calls, const double* d_loglik, int64_t n_samples,
+                           const double* d_work, const double* d_logpost, const double* d_log_evidence, ed_call_post* out, void* stream);
+/* The posterior of the batch's LAST RUN, whatever model it ran (default, per-sample mixtures, ed_batch_run_bins, ed_batch_run_cov):
+ * only the run's likelihood matrix and the plan are read.  Made on request, as the byte path is: a run invalidates it; the first of
+ * these four entries called afterwards enqueues the two passes on the stream the run's results become available on (under an
+ * asynchronous tail the batch's next run waits for them too); later calls launch nothing.  The buffers (40 bytes per cell + 8 per
+ * chain) are allocated, all or none, by the first request and freed with the batch.  Emit mode 2 goes through the
+ * [n_exons][3][n_samples] form of the matrix (as ed_batch_loglik does: conversion enqueued, form allocated once); a reader of the
+ * sample-major matrix is not implemented.  Fused mode with ed_batch_keep_loglik(batch, 0): ED_ERR_STATE.  Not for two threads at a time.
+ *   ed_batch_copy_posterior      host [n_exons][2][n_samples]: log gamma of deletion, duplication (synchronises)
+ *   ed_batch_posterior           the same as a device pointer; the first call after a run WAITS for the passes; NULL + ed_last_error()
+ *   ed_batch_copy_log_evidence   host [n_chrom][n_samples]
+ *   ed_batch_copy_call_posterior host_post[i] belongs to call i of ed_batch_copy_calls
+ *   ed_batch_n_posterior_passes  how often the passes have been enqueued on this batch since it was created */
+int ed_batch_copy_posterior(ed_batch* batch, double* host_logpost /* [n_exons][2][n_samples] */);
+const double* ed_batch_posterior(const ed_batch* batch);
+int ed_batch_copy_log_evidence(ed_batch* batch, double* host_log_evidence /* [n_chrom][n_samples] */);
+int ed_batch_copy_call_posterior(ed_batch* batch, ed_call_post* host_post, int64_t cap);
+int64_t ed_batch_n_posterior_passes(const ed_batch* batch);
+/* with ed_batch_enable_timing(batch, 1): milliseconds of the backward pass, the forward pass and (if ed_batch_copy_call_posterior has been
+ * called since) the per-call kernel of the last run's posterior request, from events on its stream; 0 for what was not timed.  Synchronises. */
+int ed_batch_posterior_ms(ed_batch* batch, float ms[3]);
+
 /* Self-check of the emissions of the last ed_batch_run (default model, two-kernel mode or fused mode with the
  * matrix kept).  ed_batch_run evaluates a cell's three log-likelihoods through per-sample hoisted constants, per-sample
  * tables and route binning; this entry evaluates every cell again ON THE DEVICE with the reference's own loop
