@@ -821,7 +821,7 @@ int fit_bins_hist_issue(ed_batch* b, const int32_t* d_test, const int32_t* d_ref
   hipLaunchKernelGGL(k_lh_select, gq, bq, 0, st, w.rhist, S, lo - 1, hi - 1, w.x0, w.x1, w.flags);
   hipLaunchKernelGGL(k_bins_edges, g1, b1, 0, st, w.x0, w.x1, w.xmax, h, B, S, d_edges);
   // ---- start: the converged single-dispersion fit, every level at that dispersion ----
-  if (int rc = fit_columns(fw, d_test, S, 1, d_ref, S, E, S, d_phi_bins, d_expected, st, true)) return rc;
+  if (int rc = fit_columns(fw, FitJob::exon_major(d_test, d_ref, S).over(E, S).into(d_phi_bins, d_expected).by_method(1), st)) return rc;
   hipLaunchKernelGGL(k_fitb_from_plain, g1, b1, 0, st, fw.eta, fw.lam, B, S, w.eta, w.lam, w.state);
   // ---- per-level histograms, the lists, the populations ----
   const int KS = (B <= 3) ? 4 : (B <= 7) ? 2 : 1;
@@ -982,7 +982,7 @@ try {
     if (int rc = batch_fitwork(b, E, S)) return rc;
     FitWork& w = *b->fitw;
     // (d_phi_bins' first row and d_expected serve as scratch outputs of the plain fit; both are rewritten below)
-    if (int rc = fit_columns(w, d_test, S, 1, d_ref, S, E, S, d_phi_bins, d_expected, st, true)) return rc;
+    if (int rc = fit_columns(w, FitJob::exon_major(d_test, d_ref, S).over(E, S).into(d_phi_bins, d_expected).by_method(1), st)) return rc;
     hipLaunchKernelGGL(k_fitb_from_plain, g1, b1, 0, st, w.eta, w.lam, B, S, eta, lam, dstate.as<double>());
   }
   // Newton from the converged single-dispersion fit: a few cheap passes over every 16th exon bring the levels' dispersions

@@ -262,7 +262,7 @@ try {
   // start: the converged intercept-only model (the histogram fit: robust from any start, ~1.6 ms), slopes 0 -- the
   // covariate effects are corrections, so the Newton iteration below begins inside its region of convergence.
   // (Started from the pooled moments it wandered off on a 953-exon case the randomised sweep produced.)
-  if (int rc = fit_columns(w, d_test, S, 1, d_ref, S, E, S, d_phi, dpar.as<double>() /* scratch: expected */, st, true)) return rc;
+  if (int rc = fit_columns(w, FitJob::exon_major(d_test, d_ref, S).over(E, S).into(d_phi, dpar.as<double>() /* scratch: expected */).by_method(1), st)) return rc;
   hipLaunchKernelGGL(k_fitc_init, g1, b1, 0, st, w.eta, w.lam, K, S, dpar.as<double>(), dstate.as<double>(), w.done);
   for (int it = 0; it < 40; ++it) {
     switch (K) {

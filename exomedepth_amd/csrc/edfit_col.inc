@@ -1,5 +1,5 @@
-// edfit_col.inc -- a column's dispersion fit on the TAIL COUNTS of its three count histograms, one workgroup per column (round 6).  Included by edcore.hip
-// after fit_newton_step; used by the cohort reference sets' chunk loop (edrefcohort.inc: k_rc_column, where the scheme is described).
+// edfit_col.inc -- a column's dispersion fit on the TAIL COUNTS of its three count histograms, one workgroup per column (round 6).  Included by edfit.inc
+// after the kernels of the per-cell and histogram forms (it needs fit_newton_step); used by the cohort reference sets' chunk loop (edrefcohort.inc: k_rc_column, where the scheme is described).
 //
 //   sum_cells [psi(a + y) - psi(a)] = sum_k T_y(k) / (a + k),   T_y(k) = #cells with y > k        (psi': squares; r with b, n = y + r with a + b)
 //

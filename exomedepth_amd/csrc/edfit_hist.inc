@@ -1,9 +1,9 @@
-// edfit_hist.inc -- the histogram form of the dispersion fit (k_fit_hist + k_fit_hnewton), included by edcore.hip once
+// edfit_hist.inc -- the histogram form of the dispersion fit (k_fit_hist + k_fit_hnewton), included by edfit.inc once
 // per GEOMETRY inside its own namespace with ED_HG_KS = samples per workgroup of k_fit_hist = 8, 4, 2: the 147 KB of LDS
 // bins are shared by that many samples, so the unit bins reach 1024 / 4096 / 4096 (y / r / n) at 8 samples and two or
 // four times as far at 4 or 2 -- deeper data (counts beyond the bins are evaluated cell by cell, which is what made a
-// fit at ~400 reads per exon and sample cost 10 ms instead of 1.3).  fit_columns launches the geometry the previous fit's
-// depth points to (all three the first time); a device word set from THIS fit's data (k_fit_start: the largest
+// fit at ~400 reads per exon and sample cost 10 ms instead of 1.3).  fit_columns launches, through the Launch struct at the end
+// of this file, the geometry the previous fit's depth points to (all three the first time: fitjob::launched_geometries); a device word set from THIS fit's data (k_fit_start: the largest
 // per-sample mean total) decides on the device which of the launched ones runs (fit_hist_runs): no host round trip.
 constexpr int kHistId = ED_HG_KS;                        // the geometry: 8, 4 or 2 = samples that share 147 KB worth of bins
 constexpr int kHistSamples = kHistId;                    // samples per workgroup of k_fit_hist
@@ -981,3 +981,36 @@ k_fit_hnm(const uint32_t* __restrict__ hist, int32_t* __restrict__ ov_y, int32_t
     exp_out[s] = 1.0 / (1.0 + ed_pexp(-eta[s]));
   }
 }
+
+// ---- host side: this geometry's launches (fit_columns calls them for hg8, hg4, hg2 in turn) ----
+struct Launch {
+  static constexpr int kIndex = kHistId == 8 ? 0 : (kHistId == 4 ? 1 : 2);   // this geometry's place in the workspace's caps
+  // cells per (row group, sample) list for fits of up to E rows: ~1/3 of the group's rows, and lists x cap < 65536 (the 16-bit second-level bins
+  // of k_fit_hnewton count the cells of all lists of a sample)
+  static int64_t cap_of(int64_t E) { return std::min<int64_t>(65535 / kHistGroups, std::max<int64_t>(8, (E / kHistGroups) / 3 + 1)); }
+  static bool on(const FitHistArgs& a) { return (a.launched & fit_hist_bit(kHistId)) != 0; }
+  static void hist(const FitHistArgs& a)
+  {
+    const FitJob& j = a.j;
+    if (j.sample_major())
+      hipLaunchKernelGGL(k_fit_hist_sm, dim3((unsigned)j.S), dim3(kHsBlock), 0, a.st, j.test, j.ref, j.sm_pitch, j.trs, j.E, j.S, a.hist, a.ov_y, a.ov_r,
+                         a.ovn, a.cap[kIndex], a.depth, a.launched, j.cb);
+    else
+      hipLaunchKernelGGL(k_fit_hist, dim3((unsigned)((((j.S + kHistSamples - 1) / kHistSamples * kHistHalves + 7) / 8) * 8)), dim3(kHistBlock), 0, a.st,
+                         j.test, j.ref, j.rrs, j.E, j.S, a.hist, a.ov_y, a.ov_r, a.ovn, a.cap[kIndex], a.depth, a.launched);
+  }
+  static void nm(const FitHistArgs& a)
+  {
+    const FitJob& j = a.j;
+    hipLaunchKernelGGL(k_fit_hnm, dim3((unsigned)((j.S + kHnS - 1) / kHnS)), dim3(kHnS, kHnY), 0, a.st, a.hist, a.ov_y, a.ov_r, a.ovn, a.cap[kIndex], j.S,
+                       a.eta, a.lam, a.done, 2000 /* optim(control = list(maxit = 2000)) */, j.test, j.ref, a.cell_rs(), j.E, a.depth, a.launched,
+                       a.fevals, a.cell_cs(), j.phi, j.expected, j.sample_major() ? 1 : 0, j.cb);
+  }
+  static void newton(const FitHistArgs& a)
+  {
+    const FitJob& j = a.j;
+    hipLaunchKernelGGL(k_fit_hnewton, dim3((unsigned)((j.S + kHnS - 1) / kHnS)), dim3(kHnS, kHnY), 0, a.st, a.hist, a.ov_y, a.ov_r, a.ovn, a.cap[kIndex], j.S,
+                       a.eta, a.lam, a.done, 100, 1e-9 /* iterations are cheap here: converge tightly */, j.test, j.ref, a.cell_rs(), j.E, a.depth,
+                       a.launched, a.cell_cs(), j.phi, j.expected, j.sample_major() ? 1 : 0, j.cb);
+  }
+};

@@ -1037,8 +1037,7 @@ static int refcohort_impl(const int32_t* d_counts, int64_t n_bins, int64_t n_sam
       if (int rc = g_rc_scratch.fit_work(n, R, &wp)) return rc;
       FitWork& w = *wp;
       tick("fit workspace");
-      const int rc = fit_columns(w, dXp.as<int32_t>(), T, 1, dcum.as<int32_t>(), R, n, R, dphi.as<double>(), dp.as<double>(), st, 0, 0, T, K,
-                                 dskip.as<int>());
+      const int rc = fit_columns(w, FitJob::cyclic_test(dXp.as<int32_t>(), T, dcum.as<int32_t>(), R, K, dskip.as<int>()).over(n, R).into(dphi.as<double>(), dp.as<double>()), st);
       if (int rc2 = link.sync(st)) return rc2;
       tick("batched fit");
       if (rc) return rc;

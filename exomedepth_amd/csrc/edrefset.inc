@@ -813,7 +813,7 @@ static int refset_part_impl(const int32_t* d_test, const int32_t* d_refs, int64_
   {
     FitWork w;
     if (int rc = w.alloc(n, Rw)) return rc;
-    const int rc = fit_columns(w, dtsel.as<int32_t>(), 1, 0, dcum.as<int32_t>(), Rw, n, Rw, dphi.as<double>(), dp.as<double>(), st);
+    const int rc = fit_columns(w, FitJob::shared_test(dtsel.as<int32_t>(), dcum.as<int32_t>(), Rw).over(n, Rw).into(dphi.as<double>(), dp.as<double>()), st);
     HIP_TRY(hipStreamSynchronize(st));
     if (rc) return rc;
   }

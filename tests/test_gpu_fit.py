@@ -303,3 +303,57 @@ def test_sample_major_histograms_with_bins_that_leave_the_lds_early(edlib, oracl
     for s in (0, 2):
         op, oe = oracle.fit_mle_hist(test[:, s], ref[:, s])[:2]
         assert abs(p1[s] - op) / op < 1e-6 and abs(e1[s] - oe) / oe < 1e-8
+
+
+def test_a_refused_fit_enqueues_nothing(edlib):
+    """fit_columns checks a request (csrc/ed_fit_job.hpp) before it enqueues anything: a refused fit leaves the caller's outputs untouched and the
+    batch's fit workspace as it was -- a valid fit issued afterwards gives the bits of the same fit on a fresh batch."""
+    from exomedepth_amd import synth
+    from exomedepth_amd._lib import EdError, check, lib
+    E, S = 64, 3
+    chrom_off, start, end = synth.exon_design(E, 1, 71)
+    test, ref, _, _, _ = synth.counts_numpy(chrom_off, S, 71, n_segments=1)
+    plan = edlib.Plan(chrom_off, start, end)
+
+    def valid_fit(batch):
+        dphi, dexp = edlib.DeviceArray(np.zeros(S)), edlib.DeviceArray(np.zeros(S))
+        batch.fit(test, ref, dphi, dexp)
+        check(lib().ed_synchronize(None))
+        return dphi.to_host(), dexp.to_host()
+
+    fresh = edlib.Batch(plan, S)
+    want_phi, want_exp = valid_fit(fresh)
+    fresh.close()
+    assert np.all(np.isfinite(want_phi)) and np.all(want_phi > 0) and np.all((want_exp > 0) & (want_exp < 1))
+
+    sentinel = -12345.678
+    dphi, dexp = edlib.DeviceArray(np.full(S, sentinel)), edlib.DeviceArray(np.full(S, sentinel))
+    batch = edlib.Batch(plan, S)
+    # (settings that make the request unservable, the counts as that request would take them, the refusal)
+    refusals = [
+        (dict(mode=1, hist=0, layout=0, bits=32), (test, ref),
+         "fit mode 1 (aod-nm) works on the count histograms: ed_batch_set_fit_histograms(batch, 0) excludes it"),
+        (dict(mode=0, hist=0, layout=1, bits=32), (np.ascontiguousarray(test.T), np.ascontiguousarray(ref.T)),
+         "fit: sample-major counts are fitted on the count histograms only (ed_batch_set_fit_histograms(batch, 0) excludes them)"),
+        (dict(mode=0, hist=1, layout=0, bits=16), (test, ref),
+         "ed_batch_fit: 16-bit counts (ed_batch_set_counts_bits(batch, 16)) come sample-major (ed_batch_set_counts_layout(batch, 1))"),
+    ]
+
+    def configure(mode, hist, layout, bits):
+        check(lib().ed_batch_set_fit_mode(batch.handle, mode))
+        batch.set_fit_histograms(hist)
+        batch.set_counts_layout(layout)
+        batch.set_counts_bits(bits)
+
+    for settings, (t, r), message in refusals:
+        configure(**settings)
+        with pytest.raises(EdError) as err:
+            batch.fit(t, r, dphi, dexp)
+        assert message in str(err.value) and "(status -5)" in str(err.value), str(err.value)      # ED_ERR_STATE
+        check(lib().ed_synchronize(None))
+        assert np.all(dphi.to_host() == sentinel) and np.all(dexp.to_host() == sentinel), settings
+    configure(mode=0, hist=1, layout=0, bits=32)
+    got_phi, got_exp = valid_fit(batch)
+    batch.close(); plan.close()
+    assert np.array_equal(got_phi.view(np.int64), want_phi.view(np.int64))
+    assert np.array_equal(got_exp.view(np.int64), want_exp.view(np.int64))
