@@ -218,6 +218,40 @@ class Plan:
         DeviceArray or a torch device tensor: the caller's own emissions are as good as a batch's.  Returns a Posterior."""
         return Posterior(self, loglik, int(n_samples), stream)
 
+    def transition_score(self, loglik, n_samples, stream=None):
+        """(log_evidence (n_chrom, n_samples), score (n_chrom, 2, n_samples)) of a likelihood matrix as Plan.posterior takes it:
+        score[:, 0, :] is d log_evidence / d transition_probability, score[:, 1, :] d log_evidence / d expected_CNV_length of every
+        (chromosome, sample) chain at this plan's values (include/exomedepth_amd.h: ed_plan_transition_score)."""
+        S, E = int(n_samples), self.n_exons
+        if not _is_device(loglik) and np.shape(loglik) != (E, 3, S):
+            raise ValueError("loglik must have shape (%d, 3, %d), got %s" % (E, S, np.shape(loglik)))
+        keep = []
+        ll = _device_pointer(loglik, np.float64, keep)
+        work = DeviceArray(nbytes=E * 3 * S * 8)
+        try:
+            return self._transition_score(ll, S, work, stream)
+        finally:
+            work.free()
+            for d in keep:
+                if isinstance(d, DeviceArray):
+                    d.free()
+
+    def _transition_score(self, ll, S, work, stream=None):
+        """... on a device pointer, with the caller's work array (n_exons * 3 * S doubles)"""
+        Cn = self.n_chrom
+        logev, score = DeviceArray(nbytes=Cn * S * 8), DeviceArray(nbytes=Cn * 2 * S * 8)
+        try:
+            check(lib().ed_plan_transition_score(self.handle, ll, S, work.ptr, logev.ptr, score.ptr, stream))
+            check(lib().ed_synchronize(stream))
+            return logev.to_host(np.float64, (Cn, S)), score.to_host(np.float64, (Cn, 2, S))
+        finally:
+            logev.free()
+            score.free()
+
+    def n_score_tables(self):
+        """times this plan has built and uploaded its table of derivatives (0 before the first score request, 1 ever after)"""
+        return int(lib().ed_plan_n_score_tables(self.handle))
+
     def close(self):
         if self.handle:
             lib().ed_plan_destroy(self.handle)
@@ -548,6 +582,24 @@ class Batch:
     def n_posterior_passes(self):
         """times the forward-backward passes have been enqueued on this batch (a second request after a run launches nothing)"""
         return int(lib().ed_batch_n_posterior_passes(self.handle))
+
+    def transition_score(self):
+        """(log_evidence (n_chrom, n_samples), score (n_chrom, 2, n_samples)) of the last run: score[:, 0, :] is
+        d log_evidence / d transition_probability, score[:, 1, :] d log_evidence / d expected_CNV_length of every chain at the plan's
+        values.  One more pass behind the posterior's, made on the first request."""
+        out = np.empty((self.plan.n_chrom, 2, self.n_samples), dtype=np.float64)
+        check(lib().ed_batch_copy_transition_score(self.handle, _ptr(out)))
+        return self.log_evidence(), out
+
+    def n_score_passes(self):
+        """times the score pass has been enqueued on this batch (a second request after a run launches nothing)"""
+        return int(lib().ed_batch_n_score_passes(self.handle))
+
+    def transition_score_ms(self):
+        """with enable_timing(): milliseconds of the last run's score pass (0: not timed)"""
+        ms = C.c_float(0)
+        check(lib().ed_batch_transition_score_ms(self.handle, C.byref(ms)))
+        return float(ms.value)
 
     def loglik(self):
         """(n_exons, 3, n_samples): [:,0,:] deletion, [:,1,:] normal, [:,2,:] duplication."""
@@ -1016,6 +1068,185 @@ class MultiDevice:
 # ---------------------------------------------------------------------------------------------
 # exon ordering of CallCNVs (reference R/class_definition.R:323-336)
 # ---------------------------------------------------------------------------------------------
+# ---------------------------------------------------------------------------------------------
+# maximum-likelihood fit of the HMM's two transition parameters (no counterpart in the reference)
+# ---------------------------------------------------------------------------------------------
+def _vmmin(fn, x0, reltol, max_iter, trace):
+    """R optim's BFGS (src/appl/optim.c: vmmin) for a function that returns its value and gradient together: inverse-Hessian update,
+    backtracking line search (step 1, x 0.2, sufficient decrease 1e-4), restart from the identity when the update is refused, stop
+    when an accepted step changes f by no more than reltol (|f| + reltol).  A trial whose value is not finite is a failed step.
+    Returns (x, f, iterations, evaluations, converged)."""
+    n = len(x0)
+    b = np.array(x0, dtype=np.float64)
+    f, g = fn(b)
+    if not np.isfinite(f):
+        raise ValueError("the objective is not finite at the starting values")
+    evals, iters, gradcount = 1, 0, 1
+    ilast = gradcount
+    B = np.eye(n)
+    converged = False
+    while True:
+        if ilast == gradcount:
+            B = np.eye(n)
+        t = -B.dot(g)
+        gradproj = float(t.dot(g))
+        count = 0
+        if gradproj < 0.0:
+            step, accepted, f_new, g_new, b_new = 1.0, False, f, g, b
+            while True:
+                b_new = b + step * t
+                count = int(np.sum(10.0 + b == 10.0 + b_new))
+                if count == n:
+                    break
+                f_new, g_new = fn(b_new)
+                evals += 1
+                accepted = bool(np.isfinite(f_new)) and f_new <= f + gradproj * step * 1e-4
+                trace.append({"x": b_new.copy(), "value": float(f_new), "accepted": accepted})
+                if accepted:
+                    break
+                step *= 0.2
+            if accepted:
+                enough = abs(f_new - f) > reltol * (abs(f) + reltol)
+                c = g_new - g
+                tt = step * t
+                b, f, g = b_new, f_new, g_new
+                gradcount += 1
+                iters += 1
+                if not enough:
+                    converged = True
+                    break
+                D1 = float(tt.dot(c))
+                if D1 > 0.0:
+                    X = B.dot(c)
+                    D2 = 1.0 + float(c.dot(X)) / D1
+                    B = B + (D2 * np.outer(tt, tt) - np.outer(tt, X) - np.outer(X, tt)) / D1
+                else:
+                    ilast = gradcount
+            elif ilast < gradcount:      # no step along this direction: once more from the identity
+                ilast = gradcount
+                continue
+            else:                        # ... and none along the gradient either
+                converged = True
+                break
+        elif ilast == gradcount:         # uphill along the gradient itself: it is zero
+            converged = True
+            break
+        else:
+            ilast = gradcount
+            continue
+        if iters >= max_iter:
+            break
+        if gradcount - ilast > 2 * n:
+            ilast = gradcount            # periodic restart
+    return b, f, iters, evals, converged
+
+
+def _score_sources(plan_args, loglik, n_samples):
+    """the cohort's slabs as (device pointer, n_samples, what keeps it alive); host data is uploaded once"""
+    n_exons = int(np.size(plan_args[1]))
+    items = list(loglik) if isinstance(loglik, (list, tuple)) else [loglik]
+    widths = list(n_samples) if isinstance(n_samples, (list, tuple, np.ndarray)) else [n_samples] * len(items)
+    if len(widths) != len(items):
+        raise ValueError("n_samples: one value, or one per slab")
+    out = []
+    for x, S in zip(items, widths):
+        if isinstance(x, Batch):
+            ptr = lib().ed_batch_loglik(x.handle)
+            if not ptr:
+                raise EdError("libedcore: %s" % lib().ed_last_error().decode(errors="replace"))
+            x.n_calls()                                  # (waits for the run and for the matrix's [E][3][S] form)
+            out.append((C.c_void_p(ptr), x.n_samples, x))
+            continue
+        if S is None:
+            S = int(x.shape[-1])
+        S = int(S)
+        if not _is_device(x) and np.shape(x) != (n_exons, 3, S):
+            raise ValueError("loglik must have shape (%d, 3, %d), got %s" % (n_exons, S, np.shape(x)))
+        keep = [x]
+        out.append((_device_pointer(x, np.float64, keep), S, keep))
+    return out
+
+
+def fit_transitions(chrom_off, start, end, loglik=None, n_samples=None, transition_probability=1e-4, expected_CNV_length=50000.0,
+                    reltol=None, max_iter=100, evaluate=None, device=0):
+    """Maximum-likelihood fit of the HMM's transition probability t and expected CNV length L on a cohort: maximises
+    l(t, L) = the sum of the log-evidence of every (sample, chromosome) chain, from the given starting values.
+
+    loglik: a likelihood matrix (n_exons, 3, n_samples) as Plan.posterior takes it (host data, a DeviceArray, a torch device tensor),
+    a Batch that has run, or a list of these for a cohort of several slabs (n_samples then one value or one per slab; a Batch and
+    anything with a shape know theirs).  Each evaluation is a fresh Plan at the trial values and one Plan.transition_score per slab;
+    a plan the library refuses (a padded position beyond 32 bits) is a failed trial step.  The search is R optim's BFGS with its
+    backtracking line search on x = (logit t, log L), in numpy; reltol defaults to sqrt(2^-52) with optim's stopping rule.
+    evaluate: a callable (t, L) -> (l, dl/dt, dl/dL) that stands for the device evaluation.
+
+    Returns a dict: transition_probability, expected_CNV_length, log_evidence (at the end), log_evidence_start, iterations,
+    evaluations, converged, trace (every evaluation: t, L, log_evidence, accepted)."""
+    if reltol is None:
+        reltol = float(np.sqrt(2.0 ** -52))
+    plan_args = (_i32(chrom_off), _i32(start), _i32(end))
+    sources, works = None, {}
+    if evaluate is None:
+        if loglik is None:
+            raise ValueError("fit_transitions: a likelihood matrix (or `evaluate`) is needed")
+        sources = _score_sources(plan_args, loglik, n_samples)
+
+        def evaluate(t, L):
+            try:
+                plan = Plan(plan_args[0], plan_args[1], plan_args[2], t, L, device)
+            except EdError:
+                return np.inf, 0.0, 0.0               # refused: a failed trial step
+            try:
+                tot = np.zeros(3)
+                for k, (ptr, S, _) in enumerate(sources):
+                    if S not in works:
+                        works[S] = DeviceArray(nbytes=plan.n_exons * 3 * S * 8)
+                    ev, sc = plan._transition_score(ptr, S, works[S])
+                    if not np.all(np.isfinite(ev)):
+                        c, s = (int(v) for v in np.argwhere(~np.isfinite(ev))[0])
+                        raise ValueError("fit_transitions: the log-evidence of the chain of chromosome %d, sample %d%s is %r at "
+                                         "transition_probability = %r, expected_CNV_length = %r"
+                                         % (c, s, " of slab %d" % k if len(sources) > 1 else "", float(ev[c, s]), t, L))
+                    tot += (ev.sum(), sc[:, 0, :].sum(), sc[:, 1, :].sum())
+                return float(tot[0]), float(tot[1]), float(tot[2])
+            finally:
+                plan.close()
+
+    calls = []
+
+    def fn(x):
+        with np.errstate(over="ignore", under="ignore"):
+            t, L = float(1.0 / (1.0 + np.exp(-x[0]))), float(np.exp(x[1]))
+        if not (0.0 < t < 1.0 and 0.0 < L < np.inf):
+            calls.append((t, L, -np.inf))
+            return np.inf, np.zeros(2)
+        l, dt, dL = evaluate(t, L)
+        calls.append((t, L, float(l)))
+        if not (np.isfinite(l) and np.isfinite(dt) and np.isfinite(dL)):
+            return np.inf, np.zeros(2)
+        return -float(l), -np.array([dt * t * (1.0 - t), dL * L])
+
+    t0, L0 = float(transition_probability), float(expected_CNV_length)
+    if not (0.0 < t0 < 1.0 and 0.0 < L0 < np.inf):
+        raise ValueError("fit_transitions: starting values must satisfy 0 < transition_probability < 1, 0 < expected_CNV_length")
+    steps = []
+    try:
+        x, f, iters, evals, converged = _vmmin(fn, (np.log(t0 / (1.0 - t0)), np.log(L0)), float(reltol), int(max_iter), steps)
+    finally:
+        for w in works.values():
+            w.free()
+        for _, _, keep in (sources or ()):
+            if isinstance(keep, list):
+                for d in keep[1:]:
+                    if isinstance(d, DeviceArray):
+                        d.free()
+    trace = [{"transition_probability": calls[0][0], "expected_CNV_length": calls[0][1], "log_evidence": calls[0][2], "accepted": True}]
+    for (t, L, l), s in zip(calls[1:], steps):
+        trace.append({"transition_probability": t, "expected_CNV_length": L, "log_evidence": l, "accepted": s["accepted"]})
+    return {"transition_probability": float(1.0 / (1.0 + np.exp(-x[0]))), "expected_CNV_length": float(np.exp(x[1])),
+            "log_evidence": -float(f), "log_evidence_start": float(calls[0][2]), "iterations": int(iters), "evaluations": int(evals),
+            "converged": bool(converged), "trace": trace}
+
+
 def chromosome_order(chromosome, start, end):
     """Return (order, chrom_levels, chrom_codes_sorted, chrom_off).  Levels are '1'..'22' first (those
     present), then the other names in first-seen order; exons are ordered by (level, midpoint) with
@@ -1213,6 +1444,18 @@ class ExomeDepth:
                                   "post.all": float(q["log_p_all"]), "log.evidence": float(q["log_evidence"])})
         self.CNV_calls = calls
         return self
+
+    def fit_transitions(self, chromosome, start, end, transition_probability=1e-4, expected_CNV_length=50000.0, **options):
+        """Maximum-likelihood transition_probability and expected_CNV_length of this sample's likelihood slot (fit_transitions on one
+        sample; not in the reference).  Exons are ordered as CallCNVs orders them; nothing of the object is changed.  Returns
+        fit_transitions' dict."""
+        n = self.likelihood.shape[0]
+        if not (len(start) == len(chromosome) == len(end) == n):
+            raise ValueError("The annotation vectors must have the same length as the data in the ExomeDepth x")
+        order, _, _, chrom_off = chromosome_order(chromosome, start, end)
+        ll = np.ascontiguousarray(np.asarray(self.likelihood, dtype=np.float64)[order]).reshape(n, 3, 1)
+        return fit_transitions(chrom_off, np.asarray(start)[order], np.asarray(end)[order], ll, 1, transition_probability,
+                               expected_CNV_length, **options)
 
 
     def AnnotateExtra(self, reference_annotation, min_overlap=0.5, column_name=None):

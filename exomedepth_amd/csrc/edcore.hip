@@ -52,6 +52,7 @@
 #include "ed_own.hpp"
 #include "ed_bamscan.hpp"
 #include "ed_launch_plan.hpp"
+#include "ed_hmm_score.hpp"
 
 using edown::DevBuf;
 using edown::PinBuf;
@@ -1284,6 +1285,12 @@ struct ed_plan {
   int64_t n_words = 0;
   int64_t max_words = 0;
   double c0 = 0, c1 = 0;         // log(1 - t), log(t / 2)
+  // the transition score (edscore.inc): the padded positions the table above was made from (host), and the table of its derivatives,
+  // built and uploaded by the first request under the lock
+  std::vector<int32_t> pad_pos;  // [E + 2 C]  chromosome c: m + 2 positions at chrom_off[c] + 2 c
+  mutable std::mutex score_mu;
+  mutable DevBuf<double> d_dlt;  // [(E + C)][4][4]  per exon gap and quad lane: d/dt and d/dL of the lane's two entries (ed_hmm_score.hpp)
+  mutable int64_t score_tables = 0;   // times the table has been built
 };
 
 struct FitWork;
@@ -1412,6 +1419,11 @@ struct ed_batch {
   DevBuf<ed_call_post> d_cpost;  // per-call posterior summary, grow-only (as d_info)
   Event post_ev[5];              // with `timing`: around k_fb_backward / k_fb_forward (0..2) and k_call_post (3, 4); made on first use
   bool post_timed = false, cpost_timed = false;
+  bool score_valid = false;  // `d_score` holds the transition score of the last run; a run clears it, ensure_score runs the pass (edscore.inc)
+  int64_t score_passes = 0;  // times ensure_score has enqueued it
+  DevBuf<double> d_score;    // [C][2][S] d logZ / d t, d logZ / d L of every chain; made on the first request
+  Event score_ev[2];         // with `timing`: around k_fb_score; made on first use
+  bool score_timed = false;
   bool fused = false;        // run emissions + Viterbi as ONE kernel (edfused.inc) instead of two overlapped ones
   bool keep_loglik = true;   // fused mode only: also write the [E][3][S] likelihood matrix (the S4 `likelihood` slot)
   int fit_hist = 1;          // ed_batch_fit: 1 = iterate on count histograms (one pass over the counts), geometry picked from
@@ -1631,6 +1643,7 @@ try {
   std::unique_ptr<ed_plan> guard(p);   // released on success only
   p->device = device; p->E = n_exons; p->C = n_chrom; p->tprob = transition_probability; p->L = expected_cnv_length;
   p->chrom_off.assign(chrom_off, chrom_off + n_chrom + 1);
+  p->pad_pos.assign((size_t)n_exons + 2 * (size_t)n_chrom, 0);
   // transitions <- matrix(c(1-t, t/2, t/2, .5,.5,0, .5,0,.5), byrow=TRUE)  (R/class_definition.R:343-347),
   // stored column-major as C_hmm reads it: T[j*3+k] = row k, column j
   const double t = transition_probability;
@@ -1671,6 +1684,7 @@ try {
         pos[0] = (int32_t)p_first;
         for (int64_t i = 0; i < m; ++i) pos[1 + i] = start[lo + i];
         pos[m + 1] = (int32_t)p_last;
+        std::copy(pos.begin(), pos.end(), p->pad_pos.begin() + (lo + 2 * (int64_t)c));
         fill_log_transitions(T, expected_cnv_length, pos.data(), m + 2, lt9.data());
         double* o = lt3.data() + (size_t)(lo + c) * 8;
         for (int64_t g = 0; g <= m; ++g) {
@@ -2167,6 +2181,7 @@ static int run_open(Run& r, ed_batch* b, const int32_t* d_test, const int32_t* d
   b->rows_valid = !r.tabsm;
   b->path_valid = kEagerPath && !b->fused;   // the byte path is made when it is asked for (ensure_path)
   b->post_valid = false;                      // ... and so is the posterior (ensure_post)
+  b->score_valid = false;                     // ... and the transition score (ensure_score)
   r.cl1 = b->counts_layout == 1;
   if (r.cl1 && !r.tabsm) return ed_fail(ED_ERR_STATE, "ed_batch_run: sample-major counts (ed_batch_set_counts_layout(batch, 1)) are served by emit mode 2 only");
   if (b->counts_bits == 16 && !(r.cl1 && r.tabsm)) return ed_fail(ED_ERR_STATE, "ed_batch_run: 16-bit counts (ed_batch_set_counts_bits(batch, 16)) are served by counts_layout 1 + emit mode 2 only");
@@ -2916,3 +2931,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edannot.inc"
 #include "edpost.inc"
 #include "edreadcount.inc"
+#include "edscore.inc"       // last: a kernel added at the end leaves every other symbol's code where it was (tools/isa_compare.py)

@@ -330,6 +330,32 @@ int64_t ed_batch_n_posterior_passes(const ed_batch* batch);
  * called since) the per-call kernel of the last run's posterior request, from events on its stream; 0 for what was not timed.  Synchronises. */
 int ed_batch_posterior_ms(ed_batch* batch, float ms[3]);
 
+/* ---- the score of the HMM's transition parameters ----
+ * d logZ / d t and d logZ / d L of every (sample, chromosome) chain, t the plan's transition probability and L its expected CNV
+ * length: what a maximum-likelihood fit of the two needs next to logZ itself.  One more walk over the likelihood matrix behind the
+ * backward pass (k_fb_score), deterministic as the posterior is.  The padded gaps of a chromosome (leading gap, closing step) are held
+ * fixed under d/dL: their distance is 2 L by construction.  A chain whose log-evidence is not finite (NaN emission, or no path) has a
+ * NaN score; every other chain is unaffected.  An empty chromosome's score is 0.
+ * The plan builds and uploads the table of the log-transitions' derivatives on the first request (128 bytes per exon gap), once,
+ * under a lock: ed_plan_create's cost and device memory are what they were.
+ *
+ * ed_plan_transition_score: on a caller-supplied DEVICE matrix d_loglik [n_exons][3][n_samples].  Enqueues the backward pass and the
+ *   score pass on `stream` and returns; on their completion
+ *     d_work         [n_exons][3][n_samples]  holds beta (as ed_plan_posterior leaves it)
+ *     d_log_evidence [n_chrom][n_samples]     logZ of every chain, the bits ed_plan_posterior gives
+ *     d_score        [n_chrom][2][n_samples]  row 0 d logZ / d t, row 1 d logZ / d L
+ * ed_batch_copy_transition_score: the same for the batch's LAST RUN, host [n_chrom][2][n_samples].  Made on request behind the
+ *   posterior's passes (which it requests itself and whose beta and logZ it reads); a run invalidates it, a second request launches
+ *   nothing, and under an asynchronous tail the batch's next run waits for it.  Fused mode without the matrix: ED_ERR_STATE.
+ * ed_batch_n_score_passes: how often the score pass has been enqueued on this batch; ed_plan_n_score_tables: how often the plan has
+ *   built its table of derivatives (0 or 1).  ed_batch_transition_score_ms: with ed_batch_enable_timing, k_fb_score's milliseconds. */
+int ed_plan_transition_score(const ed_plan* plan, const double* d_loglik, int64_t n_samples, double* d_work, double* d_log_evidence,
+                             double* d_score, void* stream);
+int ed_batch_copy_transition_score(ed_batch* batch, double* host_score /* [n_chrom][2][n_samples] */);
+int64_t ed_batch_n_score_passes(const ed_batch* batch);
+int64_t ed_plan_n_score_tables(const ed_plan* plan);
+int ed_batch_transition_score_ms(ed_batch* batch, float* ms);
+
 /* Self-check of the emissions of the last ed_batch_run (default model, two-kernel mode or fused mode with the
  * matrix kept).  ed_batch_run evaluates a cell's three log-likelihoods through per-sample hoisted constants, per-sample
  * tables and route binning; this entry evaluates every cell again ON THE DEVICE with the reference's own loop
