@@ -194,6 +194,9 @@ SYMBOLS = [
     ("ed_batch_n_score_passes", _i64, [_vp]),
     ("ed_plan_n_score_tables", _i64, [_vp]),
     ("ed_batch_transition_score_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("ed_plan_call_bounds", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _dbl, _vp, _vp]),
+    ("ed_batch_copy_call_bounds", C.c_int, [_vp, _dbl, _vp, _i64]),
+    ("ed_batch_call_bounds_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
 ]
 
 

@@ -30,6 +30,9 @@ CALL_INFO_DTYPE = np.dtype([("BF_raw", "<f8"), ("BF", "<f8"), ("reads_expected",
                             ("reads_ratio", "<f8")])
 assert CALL_INFO_DTYPE.itemsize == C.sizeof(EdCallInfo)
 CALL_POST_DTYPE = np.dtype([("post_mean", "<f8"), ("post_min", "<f8"), ("log_p_all", "<f8"), ("log_evidence", "<f8")])
+CALL_BOUNDS_DTYPE = np.dtype([("anchor_exon", "<i4"), ("start_lo", "<i4"), ("start_hi", "<i4"), ("end_lo", "<i4"), ("end_hi", "<i4"),
+                              ("flags", "<i4"), ("log_anchor", "<f8"), ("log_keep_start", "<f8"), ("log_keep_end", "<f8")])
+assert CALL_BOUNDS_DTYPE.itemsize == 48
 
 
 def _ptr(a):
@@ -309,6 +312,15 @@ class Posterior:
                                            self._logpost.ptr, self._logev.ptr, _ptr(out), self.stream))
         return out
 
+    def call_bounds(self, calls, level=0.95):
+        """breakpoint credible intervals of call rows (a CALL_DTYPE array) at `level`: a CALL_BOUNDS_DTYPE array
+        (include/exomedepth_amd.h: ed_plan_call_bounds)"""
+        calls = np.ascontiguousarray(calls, dtype=CALL_DTYPE)
+        out = np.zeros(calls.size, dtype=CALL_BOUNDS_DTYPE)
+        check(lib().ed_plan_call_bounds(self.plan.handle, _ptr(calls), calls.size, self._ll, self.n_samples, self._work.ptr,
+                                        self._logpost.ptr, float(level), _ptr(out), self.stream))
+        return out
+
     def free(self):
         for d in (self._work, self._logpost, self._logev):
             d.free()
@@ -578,6 +590,21 @@ class Batch:
         ms = (C.c_float * 3)()
         check(lib().ed_batch_posterior_ms(self.handle, ms))
         return dict(zip(("backward", "forward", "call_post"), (float(x) for x in ms)))
+
+    def call_bounds(self, level=0.95):
+        """breakpoint credible intervals of every call at `level` (row i belongs to row i of calls()): anchor_exon, start_lo <= start_hi
+        <= anchor_exon <= end_lo <= end_hi (global 0-based exon indices), flags, log_anchor, log_keep_start, log_keep_end.  One kernel
+        behind the posterior's passes, which are made on the first request after a run."""
+        n = self.n_calls()
+        out = np.zeros(n, dtype=CALL_BOUNDS_DTYPE)
+        check(lib().ed_batch_copy_call_bounds(self.handle, float(level), _ptr(out), n))
+        return out
+
+    def call_bounds_ms(self):
+        """with enable_timing(): milliseconds of k_call_bounds in the last call_bounds() of this run (0: not timed)"""
+        ms = C.c_float(0)
+        check(lib().ed_batch_call_bounds_ms(self.handle, C.byref(ms)))
+        return float(ms.value)
 
     def n_posterior_passes(self):
         """times the forward-backward passes have been enqueued on this batch (a second request after a run launches nothing)"""
@@ -878,10 +905,11 @@ class Cohort:
         b = Batch._view(self.plan, int(lib().ed_batch_n_samples(h)), h.value)   # the ticket's own width (a short last slab has its own batch)
         return b, pp.value, pe.value
 
-    def results(self, ticket, n_samples, path=False, loglik=False, info=True, posterior=False):
+    def results(self, ticket, n_samples, path=False, loglik=False, info=True, posterior=False, breakpoints=None):
         """host copies of a ticket's results: dict(calls, info, phi, expected[, path][, loglik]); with the option phi_bins = B > 1
         phi_bins (B, n) and edges (B + 1, n) stand where phi is.  posterior=True adds call_posterior (Batch.call_posterior) and
-        log_evidence; posterior="matrix" also the exon posteriors (Batch.posterior) as `posterior`"""
+        log_evidence; posterior="matrix" also the exon posteriors (Batch.posterior) as `posterior`; breakpoints=level adds call_bounds
+        (Batch.call_bounds at that level)"""
         b, pp, pe = self.batch(ticket)
         b.n_samples = int(n_samples)
         out = {"calls": b.calls()}
@@ -906,6 +934,8 @@ class Cohort:
             out["log_evidence"] = b.log_evidence()
             if posterior == "matrix":
                 out["posterior"] = b.posterior()
+        if breakpoints is not None:
+            out["call_bounds"] = b.call_bounds(breakpoints)
         return out
 
     def wait(self, ticket):
@@ -1341,7 +1371,7 @@ class ExomeDepth:
         col = 0 if type == "deletion" else 2
         return float(np.sum(self.likelihood[which, col] - self.likelihood[which, 1]))
 
-    def CallCNVs(self, chromosome, start, end, name, transition_probability=1e-4, expected_CNV_length=50000, posterior=False):
+    def CallCNVs(self, chromosome, start, end, name, transition_probability=1e-4, expected_CNV_length=50000, posterior=False, breakpoints=False):
         """reference R/class_definition.R:311-419: order exons, one Viterbi chain per chromosome,
         call table with start.p/end.p (1-based, global), type, nexons, start, end, chromosome, id.
 
@@ -1353,7 +1383,17 @@ class ExomeDepth:
 
         posterior=True adds four columns from the HMM's forward-backward pass (not in the reference): post.mean / post.min, the mean
         and the smallest posterior probability of the call's type over its exons; post.all, the log-probability that every exon of
-        the call is in that state; log.evidence, the log-evidence of the call's chromosome."""
+        the call is in that state; log.evidence, the log-evidence of the call's chromosome.
+
+        breakpoints=True (level 0.95) or a level in (0, 1) appends ten columns, after whatever else the call has: the credible intervals
+        of the call's two breakpoints from the same posterior (Batch.call_bounds).  start.p.lo <= start.p.hi <= end.p.lo <= end.p.hi are
+        exon positions, 1-based like start.p; start.lo / start.hi are those exons' start coordinates, end.lo / end.hi their end
+        coordinates; start.keep / end.keep the probability that the run of the call's state through its best-supported exon reaches at
+        least the call's own first / last exon.  A call that cannot be walked keeps its own positions and NaN."""
+        if breakpoints is None or isinstance(breakpoints, (bool, np.bool_)):
+            level = 0.95 if breakpoints else None
+        else:
+            level = float(breakpoints)
         if self.phi.size == 0:
             self.CNV_calls = []
             return self
@@ -1387,6 +1427,7 @@ class ExomeDepth:
                 raw = batch.calls()
                 self.Viterbi_path = batch.path()[:, 0].astype(np.int64)
                 cpost = batch.call_posterior() if posterior else None
+                cbnd = batch.call_bounds(level) if level is not None else None
             finally:
                 batch.close()
                 plan.close()
@@ -1409,15 +1450,16 @@ class ExomeDepth:
                 for r in res["calls"]:
                     raw.append({"start_exon": int(r["start.p"]) - 2 + lo, "end_exon": int(r["end.p"]) - 2 + lo,
                                 "type": int(r["type"]), "nexons": int(r["nexons"]), "chrom": c})
-            cpost = None
-            if posterior:
+            cpost = cbnd = None
+            if posterior or level is not None:
                 rows = np.zeros(len(raw), dtype=CALL_DTYPE)
                 for k in ("chrom", "start_exon", "end_exon", "type", "nexons"):
                     rows[k] = [r[k] for r in raw]
                 plan = Plan(chrom_off, start, end, transition_probability, expected_CNV_length)
                 try:
                     post = plan.posterior(np.ascontiguousarray(self.likelihood).reshape(n, 3, 1), 1)
-                    cpost = post.call_posterior(rows)
+                    cpost = post.call_posterior(rows) if posterior else None
+                    cbnd = post.call_bounds(rows, level) if level is not None else None
                     post.free()
                 finally:
                     plan.close()
@@ -1442,6 +1484,12 @@ class ExomeDepth:
                 q = cpost[len(calls) - 1]
                 calls[-1].update({"post.mean": float(q["post_mean"]), "post.min": float(q["post_min"]),
                                   "post.all": float(q["log_p_all"]), "log.evidence": float(q["log_evidence"])})
+            if cbnd is not None:
+                q = cbnd[len(calls) - 1]
+                slo, shi, elo, ehi = (int(q[k]) for k in ("start_lo", "start_hi", "end_lo", "end_hi"))
+                calls[-1].update({"start.p.lo": slo + 1, "start.p.hi": shi + 1, "end.p.lo": elo + 1, "end.p.hi": ehi + 1,
+                                  "start.lo": int(start[slo]), "start.hi": int(start[shi]), "end.lo": int(end[elo]), "end.hi": int(end[ehi]),
+                                  "start.keep": float(np.exp(q["log_keep_start"])), "end.keep": float(np.exp(q["log_keep_end"]))})
         self.CNV_calls = calls
         return self
 

@@ -1424,6 +1424,9 @@ struct ed_batch {
   DevBuf<double> d_score;    // [C][2][S] d logZ / d t, d logZ / d L of every chain; made on the first request
   Event score_ev[2];         // with `timing`: around k_fb_score; made on first use
   bool score_timed = false;
+  DevBuf<ed_call_bounds> d_cbounds;  // per-call breakpoint intervals (edbounds.inc), grow-only (as d_cpost)
+  Event bounds_ev[2];        // with `timing`: around k_call_bounds; made on first use
+  int64_t bounds_stamp = -1; // post_passes at the last timed k_call_bounds (its events belong to that posterior)
   bool fused = false;        // run emissions + Viterbi as ONE kernel (edfused.inc) instead of two overlapped ones
   bool keep_loglik = true;   // fused mode only: also write the [E][3][S] likelihood matrix (the S4 `likelihood` slot)
   int fit_hist = 1;          // ed_batch_fit: 1 = iterate on count histograms (one pass over the counts), geometry picked from
@@ -2931,4 +2934,5 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edannot.inc"
 #include "edpost.inc"
 #include "edreadcount.inc"
-#include "edscore.inc"       // last: a kernel added at the end leaves every other symbol's code where it was (tools/isa_compare.py)
+#include "edscore.inc"
+#include "edbounds.inc"      // (reads edpost.inc's results) last: a kernel added at the end leaves every other symbol's code where it was (tools/isa_compare.py)

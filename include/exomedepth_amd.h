@@ -356,6 +356,46 @@ int64_t ed_batch_n_score_passes(const ed_batch* batch);
 int64_t ed_plan_n_score_tables(const ed_plan* plan);
 int ed_batch_transition_score_ms(ed_batch* batch, float* ms);
 
+/* ---- breakpoint credible intervals of call rows ----
+ * Where does a call start and end, and how sure is that: from the posterior above, per call row of type T (1 deletion, 2 duplication).
+ *   anchor a   the exon of the row, start_exon .. end_exon, with the largest log gamma(T); ties to the lowest index, NaN ignored
+ *   extent     G_L(i) = log P(x_i .. x_a = T | data) - log gamma_a(T) for i <= a, G_R(j) the same for x_a .. x_j, j >= a; G(a) = 0.
+ *              Given x_a = T the left edge L and the right edge R of the run of T through a are independent and
+ *              P(L <= i | x_a = T) = exp G_L(i), P(R >= j | x_a = T) = exp G_R(j).
+ *   bounds     at `level` (0 < level < 1), tail = (1 - level) / 2, walking outward from a inside the row's chain: start_hi is the
+ *              outermost i such that every i' in [i, a] has G_L(i') >= log(1 - tail), start_lo the same with log(tail); end_lo and
+ *              end_hi symmetric.  start_lo <= start_hi <= a <= end_lo <= end_hi, and P(start_lo <= L <= start_hi | x_a = T) > level
+ *              (the same for R).  A walk that reaches the chain's first or last exon stops there.  The walk stops at the FIRST exon
+ *              below the threshold: in floating point G is not monotone where gamma is 1 to the last bit.
+ *   log_keep_start = G_L(start_exon), log_keep_end = G_R(end_exon): the log-probability that the run through the anchor reaches at
+ *              least the call's own first / last exon.
+ * A row of another type, or one none of whose exons has a finite log gamma(T): flags = 1, the four bounds and anchor_exon are the
+ * row's own start_exon / end_exon (anchor_exon = start_exon), the three doubles NaN.  A chain with a NaN emission: unspecified.
+ * Exon indices are global (as ed_call's).  Deterministic: a row's values are a function of the row alone -- not of the other rows,
+ * their order, or the batch width.
+ *
+ * ed_plan_call_bounds: for HOST rows `calls`, validated as ed_plan_call_posterior validates them, from the device arrays
+ *   ed_plan_posterior filled (d_work holds beta), enqueued on the same stream; waits and writes out[0 .. n_calls).  One more limit than
+ *   the posterior's entry has: n_calls <= 2^31 - 1 (a workgroup per row), else ED_ERR_INVALID.
+ * ed_batch_copy_call_bounds: for the call table of the batch's LAST RUN (host_out[i] belongs to call i of ed_batch_copy_calls), behind
+ *   the posterior's passes, which it requests if nobody has (the rules of ed_batch_copy_call_posterior); once they are there a request,
+ *   at whatever level, launches one kernel, and ed_batch_n_posterior_passes does not move.
+ * level outside (0, 1), or NaN: ED_ERR_INVALID, nothing enqueued.
+ * ed_batch_call_bounds_ms: with ed_batch_enable_timing, that kernel's milliseconds in the last ed_batch_copy_call_bounds since the
+ *   run's posterior was made; 0 for what was not timed.  Synchronises. */
+typedef struct {
+  int32_t anchor_exon;     /* a */
+  int32_t start_lo, start_hi, end_lo, end_hi;
+  int32_t flags;           /* 1: the row cannot be walked (see above), else 0 */
+  double log_anchor;       /* log gamma_a(T) */
+  double log_keep_start;   /* G_L(start_exon) */
+  double log_keep_end;     /* G_R(end_exon) */
+} ed_call_bounds;          /* 48 bytes */
+int ed_plan_call_bounds(const ed_plan* plan, const ed_call* calls, int64_t n_calls, const double* d_loglik, int64_t n_samples,
+                        const double* d_work, const double* d_logpost, double level, ed_call_bounds* out, void* stream);
+int ed_batch_copy_call_bounds(ed_batch* batch, double level, ed_call_bounds* host_out, int64_t cap);
+int ed_batch_call_bounds_ms(ed_batch* batch, float* ms);
+
 /* Self-check of the emissions of the last ed_batch_run (default model, two-kernel mode or fused mode with the
  * matrix kept).  ed_batch_run evaluates a cell's three log-likelihoods through per-sample hoisted constants, per-sample
  * tables and route binning; this entry evaluates every cell again ON THE DEVICE with the reference's own loop

@@ -29,7 +29,7 @@ def symbols(so_path):
     return out
 
 
-_PCREL = re.compile(r"^s_add_u32 (s\d+), \1, (0x[0-9a-f]+)$")
+_PCREL = re.compile(r"^s_add_u32 (s\d+|vcc_lo), \1, (0x[0-9a-f]+)$")      # (the register allocator also hands the pair's low half to vcc_lo)
 
 
 def address_shift(x, y):
