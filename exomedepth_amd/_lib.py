@@ -197,6 +197,8 @@ SYMBOLS = [
     ("ed_plan_call_bounds", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _dbl, _vp, _vp]),
     ("ed_batch_copy_call_bounds", C.c_int, [_vp, _dbl, _vp, _i64]),
     ("ed_batch_call_bounds_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("ed_plan_mixture_profile", C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+    ("ed_mix_geometry", C.c_int, [C.POINTER(_i32)]),
 ]
 
 

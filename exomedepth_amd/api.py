@@ -255,6 +255,45 @@ class Plan:
         """times this plan has built and uploaded its table of derivatives (0 before the first score request, 1 ever after)"""
         return int(lib().ed_plan_n_score_tables(self.handle))
 
+    def mixture_profile(self, test, ref, phi, expected, grid, layout=0, stream=None):
+        """The log-evidence of every (pair, chromosome) chain at every mixture of `grid`, from the counts (include/exomedepth_amd.h:
+        ed_plan_mixture_profile): (G, n_chrom, S) float64.  test / ref: int32 counts of the tumours and their normals, (n_exons, S) with
+        layout 0 or (S, n_exons) with layout 1; phi, expected: float64 (S,); host arrays, DeviceArrays or torch device tensors.  grid:
+        (G, S), every pair its own mixtures, or (G,), the same for every pair; 1 <= G <= 16."""
+        if isinstance(phi, DeviceArray) and phi.shape is None:
+            S = phi.nbytes // 8
+        else:
+            S = int(np.size(phi)) if not _is_device(phi) else int(phi.shape[0])
+        if _is_device(grid):
+            G = int(grid.shape[0])
+            if tuple(grid.shape) != (G, S):
+                raise ValueError("a device grid must have shape (G, %d), got %s" % (S, tuple(grid.shape)))
+        else:
+            grid = np.asarray(grid, dtype=np.float64)
+            if grid.ndim == 1:
+                grid = np.repeat(grid[:, None], S, axis=1)
+            if grid.ndim != 2 or grid.shape[1] != S:
+                raise ValueError("grid must have shape (G, %d) or (G,), got %s" % (S, grid.shape))
+            G = int(grid.shape[0])
+        want = (self.n_exons, S) if not layout else (S, self.n_exons)
+        for x in (test, ref):
+            if not _is_device(x) and np.shape(x) != want:
+                raise ValueError("counts must have shape %s with layout %r, got %s" % (want, layout, np.shape(x)))
+        keep = []
+        out = DeviceArray(nbytes=max(G, 1) * self.n_chrom * S * 8)
+        try:
+            pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
+            pp, pe = _device_pointer(phi, np.float64, keep), _device_pointer(expected, np.float64, keep)
+            pg = _device_pointer(grid, np.float64, keep)
+            check(lib().ed_plan_mixture_profile(self.handle, pt, pr, int(layout), S, pp, pe, pg, G, out.ptr, C.c_void_p(stream or 0)))
+            check(lib().ed_synchronize(C.c_void_p(stream or 0)))
+            return out.to_host(np.float64, (G, self.n_chrom, S))
+        finally:
+            out.free()
+            for d in keep:
+                if isinstance(d, DeviceArray):
+                    d.free()
+
     def close(self):
         if self.handle:
             lib().ed_plan_destroy(self.handle)
@@ -1277,6 +1316,154 @@ def fit_transitions(chrom_off, start, end, loglik=None, n_samples=None, transiti
             "converged": bool(converged), "trace": trace}
 
 
+def mixture_geometry():
+    """{tile, max_grid, pairs_per_workgroup, lds_bytes} of the mixture-profile kernel (ed_mix_geometry): for tests placing shapes on the edges"""
+    out = (C.c_int32 * 4)()
+    check(lib().ed_mix_geometry(out))
+    return dict(zip(("tile", "max_grid", "pairs_per_workgroup", "lds_bytes"), (int(v) for v in out)))
+
+
+MIX_GRID = 16      # grid points of a round of fit_prop_tumor's search: one launch of the profile kernel
+
+
+def _refine_grid(lo, hi):
+    """16 equally spaced values from lo to hi, both ends exactly; lo, hi (S,) -> (16, S)"""
+    k = np.arange(MIX_GRID, dtype=np.float64)[:, None] / (MIX_GRID - 1)
+    g = lo[None, :] + (hi - lo)[None, :] * k
+    g[0], g[-1] = lo, hi
+    return g
+
+
+def _first_argmax(l):
+    """first index of the largest value per column, NaN ranked below everything"""
+    return np.argmax(np.where(np.isnan(l), -np.inf, l), axis=0)
+
+
+def _prop_tumor_search(evaluate, n_pairs, lower, upper, rounds, min_gain):
+    """fit_prop_tumor's search on `evaluate`: grid (G, S) -> l (G, S).  Pure numpy, vectorised over the pairs."""
+    S = int(n_pairs)
+    lower = np.array(np.broadcast_to(np.asarray(lower, dtype=np.float64), (S,)))
+    upper = np.array(np.broadcast_to(np.asarray(upper, dtype=np.float64), (S,)))
+    if rounds < 1 or not np.all(np.isfinite(lower) & np.isfinite(upper) & (lower < upper)):
+        raise ValueError("fit_prop_tumor: rounds >= 1 and finite lower < upper are needed")
+    cols = np.arange(S)
+    grid = _refine_grid(lower, upper)
+    l = np.array(evaluate(grid), dtype=np.float64).reshape(MIX_GRID, S)
+    profile, n_eval = l.copy(), 1
+    bad = np.isnan(l).any(axis=0)
+    trace = [{"grid": grid.copy(), "values": l.copy(), "k": _first_argmax(l)}]
+    for _ in range(1, int(rounds)):
+        k = trace[-1]["k"]
+        grid = _refine_grid(grid[np.maximum(k - 1, 0), cols], grid[np.minimum(k + 1, MIX_GRID - 1), cols])
+        l = np.array(evaluate(grid), dtype=np.float64).reshape(MIX_GRID, S)
+        n_eval += 1
+        bad |= np.isnan(l).any(axis=0)
+        trace.append({"grid": grid.copy(), "values": l.copy(), "k": _first_argmax(l)})
+    if np.all(lower == 0.0):
+        null = profile[0].copy()
+    else:
+        null = np.array(evaluate(np.zeros((1, S))), dtype=np.float64).reshape(S)
+        n_eval += 1
+        bad |= np.isnan(null)
+    k = trace[-1]["k"]
+    h = grid[1] - grid[0]
+    mk, lk = grid[k, cols], l[k, cols]
+    km, kp = np.maximum(k - 1, 0), np.minimum(k + 1, MIX_GRID - 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d2 = (l[km, cols] - 2.0 * lk) + l[kp, cols]
+        vertex = (k >= 1) & (k <= MIX_GRID - 2) & (d2 < 0.0)
+        off = h * (0.5 * (l[km, cols] - l[kp, cols]) / d2)
+        m = np.where(vertex, np.clip(mk + off, grid[km, cols], grid[kp, cols]), mk)
+        se = np.where(vertex, h / np.sqrt(-d2), np.nan)
+    at_bound = ~vertex & ((mk == lower) | (mk == upper))
+    gain = lk - null
+    informative = ~bad & (gain >= min_gain)
+    nan = np.full(S, np.nan)
+    return {"prop_tumor": np.where(informative, m, nan), "estimate": np.where(bad, nan, m), "log_evidence": np.where(bad, nan, lk),
+            "log_evidence_null": np.where(bad, nan, null), "gain": np.where(bad, nan, gain), "se": np.where(bad, nan, se),
+            "informative": informative, "at_bound": at_bound & ~bad, "profile": profile, "evaluations": n_eval, "trace": trace}
+
+
+def fit_prop_tumor(chrom_off, start, end, tumor=None, normal=None, phi=None, expected=None, lower=0.0, upper=1.0, rounds=3, min_gain=5.41,
+                   transition_probability=1e-4, expected_CNV_length=50000.0, evaluate=None, device=0):
+    """Maximum-likelihood tumour fraction (prop.tumor, the mixture of the somatic model) of every tumour / normal pair: per pair s the
+    maximiser over [lower, upper] of l_s(m) = the sum over the chromosomes of the log-evidence of the pair's chains at mixture m, with the
+    transition parameters given (not in the reference, whose somatic.CNV.call takes prop.tumor on faith).
+
+    tumor, normal: counts (n_exons, n_pairs), or (n_exons,) for one pair.  phi, expected: one value per pair; when None both are fitted
+    by Batch.fit, which -- as the reference's fit -- ignores the mixture.  Every evaluation is one launch of Plan.mixture_profile at 16
+    mixtures per pair.  evaluate: a callable grid (G, n_pairs) -> l (G, n_pairs) that stands for the device (the number of pairs is
+    then taken from phi, expected, lower or upper, else 1).
+
+    The search is deterministic and runs in numpy: round 0 evaluates m_k = lower + (upper - lower) k / 15, k = 0 .. 15; every later
+    round takes k* = the first index of the largest value, brackets [m_max(k* - 1, 0), m_min(k* + 1, 15)] and evaluates 16 equally spaced
+    values with both ends; the spacing shrinks by 2 / 15 a round (three rounds: 1.2e-3 of the interval).  At the end, where k* of the
+    last grid is interior and the second difference there is negative, the estimate is the vertex of the parabola through k* - 1, k*,
+    k* + 1, clamped to the bracket, with se = spacing / sqrt(-second difference); elsewhere it is m_k*, se is NaN and at_bound says
+    whether m_k* is `lower` or `upper`.
+
+    Returns a dict of per-pair arrays: prop_tumor (NaN where the pair is not informative), estimate (the same without that mask),
+    log_evidence (the largest value of the last grid), log_evidence_null (l_s(0): from the profile when lower == 0, else one extra
+    evaluation), gain = log_evidence - log_evidence_null, se, informative (gain >= min_gain; 5.41 is half the 0.999 quantile of chi^2_1),
+    at_bound; and profile (round 0, (16, n_pairs)), evaluations, trace (per round grid, values, k).  A pair whose evidence is NaN at
+    any value evaluated (phi >= 1, expected 0 or 1) is reported NaN and not informative; the other pairs are not affected.
+
+    What the profile can identify (checked on data drawn from the model: chromosomes of up to 1 300 exons with three planted segments of
+    8 - 40 exons, two seeds): at totals around 2 000 reads and phi = 5e-4 the fractions 1.0 / 0.6 / 0.3 are recovered to the first
+    grid's spacing with gains of thousands / a thousand / hundreds of log units.  A pair without a somatic CNV, and one at a fraction of
+    0.1, gain at most 1.3: m = 0 makes the three states' emissions equal, so "no CNV" and "no tumour" are the same statement and the
+    pair is reported not informative.  At totals around 200 and phi = 2e-3 a fraction of 0.3 is not identifiable either (gain 0.07)."""
+    if evaluate is not None:
+        S = max(int(np.size(x)) for x in (phi, expected, lower, upper) if x is not None)
+        return _prop_tumor_search(evaluate, S, lower, upper, rounds, min_gain)
+    if tumor is None or normal is None:
+        raise ValueError("fit_prop_tumor: tumour and normal counts (or `evaluate`) are needed")
+    chrom_off, start, end = _i32(chrom_off), _i32(start), _i32(end)
+    E = int(start.size)
+    on_dev = _is_device(tumor) and _is_device(normal)           # int32 (n_exons, n_pairs) device arrays are used in place
+    if not on_dev:
+        tumor, normal = _i32(tumor), _i32(normal)
+        if tumor.ndim == 1:
+            tumor, normal = tumor.reshape(E, 1), normal.reshape(-1, 1)
+    if len(tumor.shape) != 2 or tumor.shape[0] != E or tuple(normal.shape) != tuple(tumor.shape):
+        raise ValueError("fit_prop_tumor: tumor and normal must both have shape (%d, n_pairs)" % E)
+    S = int(tumor.shape[1])
+    plan = Plan(chrom_off, start, end, transition_probability, expected_CNV_length, device)
+    dev = []
+    try:
+        dt, dn = (tumor, normal) if on_dev else (DeviceArray(tumor), DeviceArray(normal))
+        if not on_dev:
+            dev += [dt, dn]
+        if phi is None or expected is None:
+            dp, de = DeviceArray(np.zeros(S)), DeviceArray(np.zeros(S))
+            dev += [dp, de]
+            batch = Batch(plan, S)
+            try:
+                batch.fit(dt, dn, dp, de)
+                check(lib().ed_synchronize(None))
+                if batch.fit_unconverged()[0]:
+                    import warnings
+                    warnings.warn("beta-binomial fit: the Newton iteration did not converge (phi, expected are its last iterate)")
+            finally:
+                batch.close()
+            phi, expected = dp.to_host(), de.to_host()
+        else:
+            phi = _f64(np.broadcast_to(np.asarray(phi, dtype=np.float64), (S,)))
+            expected = _f64(np.broadcast_to(np.asarray(expected, dtype=np.float64), (S,)))
+            dp, de = DeviceArray(phi), DeviceArray(expected)
+            dev += [dp, de]
+
+        def on_device(grid):
+            return plan.mixture_profile(dt, dn, dp, de, np.ascontiguousarray(grid, dtype=np.float64)).sum(axis=1)
+        fit = _prop_tumor_search(on_device, S, lower, upper, rounds, min_gain)
+        fit["phi"], fit["expected"] = np.array(phi), np.array(expected)
+        return fit
+    finally:
+        for d in dev:
+            d.free()
+        plan.close()
+
+
 def chromosome_order(chromosome, start, end):
     """Return (order, chrom_levels, chrom_codes_sorted, chrom_off).  Levels are '1'..'22' first (those
     present), then the other names in first-seen order; exons are ordered by (level, midpoint) with
@@ -1505,6 +1692,20 @@ class ExomeDepth:
         return fit_transitions(chrom_off, np.asarray(start)[order], np.asarray(end)[order], ll, 1, transition_probability,
                                expected_CNV_length, **options)
 
+    def fit_prop_tumor(self, chromosome, start, end, **options):
+        """Maximum-likelihood tumour fraction of this pair (test = tumour, reference = normal) at the object's phi and expected:
+        fit_prop_tumor on one pair (not in the reference).  Exons are ordered as CallCNVs orders them; nothing of the object is changed.
+        Returns fit_prop_tumor's dict (arrays of length 1)."""
+        n = self.test.size
+        if not (len(start) == len(chromosome) == len(end) == n):
+            raise ValueError("The annotation vectors must have the same length as the data in the ExomeDepth x")
+        if self.phi.size == 0:
+            raise ValueError("the object has no fitted phi / expected (too few bins with reads)")
+        if not (np.all(self.phi == self.phi[0]) and np.all(self.expected == self.expected[0])):
+            raise NotImplementedError("fit_prop_tumor with a per-exon phi or expected (phi.bins > 1, covariates) is not implemented")
+        order, _, _, chrom_off = chromosome_order(chromosome, start, end)
+        return fit_prop_tumor(chrom_off, np.asarray(start)[order], np.asarray(end)[order], _as_r_integer(self.test[order]),
+                              _as_r_integer(self.reference[order]), phi=self.phi[:1], expected=self.expected[:1], **options)
 
     def AnnotateExtra(self, reference_annotation, min_overlap=0.5, column_name=None):
         """reference R/annotate_extra.R:41-73: adds `column_name` to every row of CNV_calls -- the `names` of the annotation's intervals the
@@ -1528,14 +1729,39 @@ def somatic_CNV_call(normal, tumor, prop_tumor=1.0, chromosome=None, start=None,
     """reference R/class_definition.R:442-461: one matched tumour / normal pair -- new('ExomeDepth', test = tumor, reference = normal,
     prop.tumor = prop_tumor) (the fit ignores prop_tumor; the likelihood sees it) followed by CallCNVs(transition.probability = 1e-4)
     with the default expected.CNV.length.  Returns the ExomeDepth object.  A cohort of pairs, each at its own tumour fraction:
-    Cohort.run_host / MultiDevice.run_host with test = tumours, ref = normals and one mixture per column."""
+    Cohort.run_host / MultiDevice.run_host with test = tumours, ref = normals and one mixture per column.
+
+    prop_tumor = "fit" (not in the reference): the fraction is first estimated by maximum likelihood (ExomeDepth.fit_prop_tumor, at the
+    transition parameters of the call).  The estimate is used where the pair is informative; where it is not -- no somatic CNV, too low
+    a fraction, too shallow data: see fit_prop_tumor -- 1.0 is used and a line on stderr says why.  The fit is recorded on the returned
+    object as prop_tumor_fit.  A numeric prop_tumor behaves as it always has."""
     if chromosome is None or start is None or end is None or names is None:
         raise ValueError("chromosome, start, end and names are required (R/class_definition.R:442)")
-    if np.ndim(prop_tumor) != 0:
+    fit_it = isinstance(prop_tumor, str)
+    if fit_it and prop_tumor != "fit":
+        raise ValueError('prop_tumor is a number or "fit"')
+    if not fit_it and np.ndim(prop_tumor) != 0:
         raise ValueError("prop_tumor is one value for the pair")
     sys.stderr.write("Warning: this function is largely untested and experimental\n")     # message() lines of :444-451
     sys.stderr.write("Initializing the exomeDepth object\n")
-    x = ExomeDepth(test=tumor, reference=normal, prop_tumor=prop_tumor, formula="cbind(test, reference) ~ 1")
+    if not fit_it:
+        x = ExomeDepth(test=tumor, reference=normal, prop_tumor=prop_tumor, formula="cbind(test, reference) ~ 1")
+        sys.stderr.write("Now calling the CNVs\n")
+        return x.CallCNVs(chromosome, start, end, names, transition_probability=1e-4)
+    x = ExomeDepth(test=tumor, reference=normal, prop_tumor=1.0, formula="cbind(test, reference) ~ 1")   # (the fit ignores prop_tumor)
+    fit = None
+    if x.phi.size:
+        sys.stderr.write("Fitting the tumour fraction\n")
+        fit = x.fit_prop_tumor(chromosome, start, end, transition_probability=1e-4)
+        if fit["informative"][0]:
+            m = float(fit["prop_tumor"][0])
+            sys.stderr.write("Fitted prop_tumor = %.4f (se %.2g, gain %.1f log units over prop_tumor = 0)\n" % (m, fit["se"][0], fit["gain"][0]))
+            x = ExomeDepth(test=tumor, reference=normal, phi=float(x.phi[0]), expected=float(x.expected[0]), prop_tumor=m,
+                           formula="cbind(test, reference) ~ 1")
+        else:
+            sys.stderr.write("The tumour fraction is not identifiable for this pair (gain %.2f log units over prop_tumor = 0: no somatic CNV, "
+                             "a low fraction or shallow data); using prop_tumor = 1\n" % fit["gain"][0])
+    x.prop_tumor_fit = fit
     sys.stderr.write("Now calling the CNVs\n")
     return x.CallCNVs(chromosome, start, end, names, transition_probability=1e-4)
 

@@ -53,6 +53,7 @@
 #include "ed_bamscan.hpp"
 #include "ed_launch_plan.hpp"
 #include "ed_hmm_score.hpp"
+#include "ed_mix_plan.hpp"
 
 using edown::DevBuf;
 using edown::PinBuf;
@@ -1291,6 +1292,11 @@ struct ed_plan {
   mutable std::mutex score_mu;
   mutable DevBuf<double> d_dlt;  // [(E + C)][4][4]  per exon gap and quad lane: d/dt and d/dL of the lane's two entries (ed_hmm_score.hpp)
   mutable int64_t score_tables = 0;   // times the table has been built
+  // the mixture profile (edmix.inc): its launch rows -- the non-empty chromosomes, longest first (ed_mix_plan.hpp) -- uploaded by the
+  // first request under the lock
+  mutable std::mutex mix_mu;
+  mutable DevBuf<int32_t> d_mix_jobs;
+  mutable int32_t n_mix_jobs = -1;    // -1: not made yet
 };
 
 struct FitWork;
@@ -2936,3 +2942,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edreadcount.inc"
 #include "edscore.inc"
 #include "edbounds.inc"      // (reads edpost.inc's results) last: a kernel added at the end leaves every other symbol's code where it was (tools/isa_compare.py)
+#include "edmix.inc"         // (edpost.inc's lse3) behind it for the same reason

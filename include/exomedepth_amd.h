@@ -356,6 +356,27 @@ int64_t ed_batch_n_score_passes(const ed_batch* batch);
 int64_t ed_plan_n_score_tables(const ed_plan* plan);
 int ed_batch_transition_score_ms(ed_batch* batch, float* ms);
 
+/* ---- the mixture profile: the log-evidence of tumour / normal pairs as a function of the tumour fraction ----
+ * logZ of every (pair, chromosome) chain at n_grid values of the pair's mixture (prop.tumor), evaluated from the counts: the emissions
+ * are the strict mode's, bit for bit, formed on the fly and folded into the chains' forward recurrence (k_mix_profile) -- no likelihood
+ * matrix is written, so sixteen mixtures cost one launch and 8 n_grid n_chrom n_samples bytes.  What a maximum-likelihood fit of the
+ * tumour fraction needs (fit_prop_tumor in the Python package): l_s(m) = the sum over the chromosomes of logZ(pair s, mixture m).
+ *   d_test, d_ref  DEVICE int32 counts of the tumours (test) and their normals (reference); layout 0: [n_exons][n_samples], 1: [n_samples][n_exons]
+ *   d_phi, d_expected  DEVICE double [n_samples]
+ *   d_grid         DEVICE double [n_grid][n_samples]: every pair has its own values; 1 <= n_grid <= 16
+ *   d_logev        DEVICE double [n_grid][n_chrom][n_samples]; an empty chromosome's value is 0 (as ed_plan_posterior's)
+ * Asynchronous on `stream`.  The value of a (pair, chromosome, mixture) has the same bits whatever n_samples, n_grid, the mixture's
+ * place in the grid, the other pairs and the layout; it agrees with ed_batch_copy_log_evidence after a strict run at that mixture to the
+ * posterior's bar (the one is a forward, the other a backward recurrence).  A pair outside the model's domain (phi >= 1, expected 0 or
+ * 1, a mixture that is not finite) reads NaN and changes nothing for the others.
+ * ED_ERR_INVALID before anything is enqueued: n_grid outside 1 .. 16, a layout other than 0 / 1, n_samples outside 1 .. 2^20, a NULL pointer.
+ * The plan uploads its launch rows (4 bytes per chromosome) on the first request, once, under a lock.
+ * ed_mix_geometry: out = {T, G, P, L}: a workgroup serves P pairs (1) and one chromosome, walks it in tiles of T exons at up to G grid
+ * points and holds L bytes of LDS -- for tests that place their shapes on the tile's edges.  No result depends on them. */
+int ed_plan_mixture_profile(const ed_plan* plan, const int32_t* d_test, const int32_t* d_ref, int layout, int64_t n_samples,
+                            const double* d_phi, const double* d_expected, const double* d_grid, int n_grid, double* d_logev, void* stream);
+int ed_mix_geometry(int32_t out[4]);
+
 /* ---- breakpoint credible intervals of call rows ----
  * Where does a call start and end, and how sure is that: from the posterior above, per call row of type T (1 deletion, 2 duplication).
  *   anchor a   the exon of the row, start_exon .. end_exon, with the largest log gamma(T); ties to the lowest index, NaN ignored
