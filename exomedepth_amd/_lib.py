@@ -199,6 +199,13 @@ SYMBOLS = [
     ("ed_batch_call_bounds_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("ed_plan_mixture_profile", C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     ("ed_mix_geometry", C.c_int, [C.POINTER(_i32)]),
+    ("ed_plan_power_map", C.c_int, [C.POINTER(_vp), _vp, _vp, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _dbl, _vp]),
+    ("ed_power_free", None, [_vp]),
+    ("ed_power_regions", C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    ("ed_power_copy_exons", C.c_int, [_vp, _vp, _vp]),
+    ("ed_power_copy_table", C.c_int, [_vp, _i64, _vp, _vp, _i64, C.POINTER(_i64)]),
+    ("ed_power_stats", C.c_int, [_vp, _vp, _vp]),
+    ("ed_power_geometry", C.c_int, [C.POINTER(_i32)]),
 ]
 
 

@@ -294,6 +294,12 @@ class Plan:
                 if isinstance(d, DeviceArray):
                     d.free()
 
+    def power_map(self, test, ref, phi, expected, mixture=1.0, layout=0, stream=None):
+        """The detection-power map of the samples (include/exomedepth_amd.h: ed_plan_power_map): a PowerMap.  test / ref: int32 counts,
+        (n_exons, S) with layout 0 or (S, n_exons) with layout 1 -- host arrays, or both DeviceArrays / torch device tensors; phi, expected:
+        one value per sample (host); mixture: a scalar or one value per sample."""
+        return PowerMap(self, test, ref, phi, expected, mixture, layout, stream)
+
     def close(self):
         if self.handle:
             lib().ed_plan_destroy(self.handle)
@@ -1464,6 +1470,219 @@ def fit_prop_tumor(chrom_off, start, end, tumor=None, normal=None, phi=None, exp
         plan.close()
 
 
+# ---------------------------------------------------------------------------------------------
+# detection power: the expected Bayes factor of a CNV per exon and per region
+# ---------------------------------------------------------------------------------------------
+POWER_DTYPE = np.dtype([("chrom", "<i4"), ("first_exon", "<i4"), ("last_exon", "<i4"), ("n_exons", "<i4"), ("n_empty", "<i4"),
+                        ("mean_del", "<f8"), ("var_del", "<f8"), ("mean_dup", "<f8"), ("var_dup", "<f8"), ("price", "<f8"),
+                        ("threshold", "<f8"), ("power_del", "<f8"), ("power_dup", "<f8")])
+
+
+def power_geometry():
+    """{walk_tile, occupancy_cap, max_total, region_tile} of the detection-power kernels (ed_power_geometry): for tests placing shapes on the edges"""
+    out = (C.c_int32 * 4)()
+    check(lib().ed_power_geometry(out))
+    return dict(zip(("walk_tile", "occupancy_cap", "max_total", "region_tile"), (int(v) for v in out)))
+
+
+def _normal_cdf(z):
+    try:
+        from scipy.special import ndtr
+        return ndtr(z)
+    except ImportError:
+        import math
+        return np.frompyfunc(lambda v: 0.5 * math.erfc(-v / math.sqrt(2.0)) if v == v else v, 1, 1)(z).astype(np.float64)
+
+
+def power_from_moments(mean, var, threshold):
+    """P(sum of the exons' Bayes-factor terms > threshold) when the region truly carries the CNV, by the NORMAL APPROXIMATION of a sum
+    of independent exon terms: Phi((mean - threshold) / sqrt(var)).  Where var is 0 the result is 1 or 0 by the sign of mean - threshold
+    (0 where they are equal); NaN stays NaN.  A few exons at low depth are far from normal: read the figure as a guide there."""
+    mean, var, threshold = np.broadcast_arrays(np.asarray(mean, np.float64), np.asarray(var, np.float64), np.asarray(threshold, np.float64))
+    d = mean - threshold
+    out = np.full(d.shape, np.nan)
+    ok = ~(np.isnan(d) | np.isnan(var))
+    pos = ok & (var > 0)
+    out[pos] = _normal_cdf(d[pos] / np.sqrt(var[pos]))
+    flat = ok & ~(var > 0)
+    out[flat] = (d[flat] > 0).astype(np.float64)
+    return out
+
+
+def _region_rows(rows):
+    """call-shaped rows from a CALL_DTYPE array (or any structured array with chrom, start_exon, end_exon) or from (chrom, first, last) triples"""
+    a = np.asarray(rows)
+    if a.dtype.names:
+        out = np.zeros(a.size, dtype=CALL_DTYPE)
+        for k in ("chrom", "start_exon", "end_exon"):
+            out[k] = a[k].ravel()
+        return out
+    a = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("region rows must fit 32-bit integers")
+    out = np.zeros(a.shape[0], dtype=CALL_DTYPE)
+    out["chrom"], out["start_exon"], out["end_exon"] = a[:, 0], a[:, 1], a[:, 2]
+    return out
+
+
+class PowerMap:
+    """Device-resident detection-power map of Plan.power_map: per sample the table of (total, mean_del, var_del, mean_dup, var_dup) of
+    its occupied totals, and per (sample, exon) the table slot of the exon's total.  mean_T is the expected contribution of an exon to a
+    call's BF column when the exon truly is in state T, var_T its variance (include/exomedepth_amd.h)."""
+
+    def __init__(self, plan, test, ref, phi, expected, mixture=1.0, layout=0, stream=None):
+        self.plan, self.stream = plan, stream
+        phi, expected = _f64(np.atleast_1d(phi)), _f64(np.atleast_1d(expected))
+        S = int(phi.size)
+        if expected.size != S:
+            raise ValueError("phi and expected must have one value per sample")
+        self.n_samples = S
+        mix = _per_sample_mixture(mixture, S)
+        on_dev = _is_device(test) and _is_device(ref)
+        if not on_dev and (_is_device(test) or _is_device(ref)):
+            raise ValueError("test and ref must both be device arrays or both be host arrays")
+        want = (plan.n_exons, S) if not layout else (S, plan.n_exons)
+        keep = []
+        if on_dev:
+            pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
+        else:
+            test, ref = _i32(test), _i32(ref)
+            for x in (test, ref):
+                if x.shape != want:
+                    raise ValueError("counts must have shape %s with layout %r, got %s" % (want, layout, x.shape))
+            pt, pr = _ptr(test), _ptr(ref)
+        self.handle = C.c_void_p()
+        check(lib().ed_plan_power_map(C.byref(self.handle), plan.handle, pt, pr, int(on_dev), int(layout), S, _ptr(phi), _ptr(expected),
+                                      _ptr(mix) if mix is not None else None, 1.0 if mix is not None else float(mixture),
+                                      C.c_void_p(stream or 0)))
+
+    def regions(self, rows, threshold=None):
+        """Per (region, sample): a POWER_DTYPE array of shape (n_regions, n_samples).  rows: a call table (CALL_DTYPE; chrom, start_exon
+        and end_exon are read) or (chrom, first_exon, last_exon) triples -- a contiguous run of exons inside one chromosome of the plan;
+        a row of (chrom, -1, -1) stands for a region with no exon inside (region_runs makes such rows): n_exons 0, sums 0, price NaN.
+        mean_T / var_T are the sums over the run's exons, n_empty counts its exons without reads, price is the evidence at which
+        Viterbi prefers exactly this segment to all normal; power_T = power_from_moments(mean_T, var_T, threshold) with threshold =
+        price unless given (a scalar or one value per region)."""
+        rows = _region_rows(rows)
+        R, S = rows.size, self.n_samples
+        none = (rows["start_exon"] == -1) & (rows["end_exon"] == -1)
+        live = np.ascontiguousarray(rows[~none])
+        n = int(live.size)
+        sums, empty = np.zeros((4, n, S)), np.zeros((n, S), dtype=np.int32)
+        price, nex = np.zeros(n), np.zeros(n, dtype=np.int32)
+        check(lib().ed_power_regions(self.handle, _ptr(live), n, _ptr(sums), _ptr(empty), _ptr(price), _ptr(nex), C.c_void_p(self.stream or 0)))
+        out = np.zeros((R, S), dtype=POWER_DTYPE)
+        out["chrom"], out["first_exon"], out["last_exon"] = rows["chrom"][:, None], rows["start_exon"][:, None], rows["end_exon"][:, None]
+        out["price"][none] = np.nan
+        at = np.flatnonzero(~none)
+        out["n_exons"][at], out["n_empty"][at], out["price"][at] = nex[:, None], empty, price[:, None]
+        for c, k in enumerate(("mean_del", "var_del", "mean_dup", "var_dup")):
+            out[k][at] = sums[c]
+        thr = out["price"] if threshold is None else np.broadcast_to(np.asarray(threshold, dtype=np.float64).reshape(-1, 1), (R, 1))
+        out["threshold"] = thr
+        out["power_del"] = power_from_moments(out["mean_del"], out["var_del"], out["threshold"])
+        out["power_dup"] = power_from_moments(out["mean_dup"], out["var_dup"], out["threshold"])
+        return out
+
+    def exons(self):
+        """(4, n_samples, n_exons): mean_del, var_del, mean_dup, var_dup of every exon; NaN where the total was skipped or the sample is
+        outside the model"""
+        out = np.zeros((4, self.n_samples, self.plan.n_exons))
+        check(lib().ed_power_copy_exons(self.handle, _ptr(out), C.c_void_p(self.stream or 0)))
+        return out
+
+    def table(self, sample):
+        """the sample's table: dict of totals (ascending, int32) and mean_del, var_del, mean_dup, var_dup"""
+        n = C.c_int64(0)
+        check(lib().ed_power_copy_table(self.handle, int(sample), None, None, 0, C.byref(n)))
+        k = int(n.value)
+        totals, values = np.zeros(k, dtype=np.int32), np.zeros((4, max(k, 1)))
+        if k:
+            check(lib().ed_power_copy_table(self.handle, int(sample), _ptr(totals), _ptr(values), k, C.byref(n)))
+        return {"totals": totals, "mean_del": values[0, :k].copy(), "var_del": values[1, :k].copy(), "mean_dup": values[2, :k].copy(),
+                "var_dup": values[3, :k].copy()}
+
+    def stats(self):
+        """n_samples, n_exons, n_jobs (occupied totals over all samples), max_jobs (of one sample), n_skipped (cells whose total is above
+        the largest one walked), n_bad_samples (parameters outside the model), largest_total, map_words; occupancy_ms, walk_ms,
+        regions_ms, exons_ms (the last call of each), host-timed between waits"""
+        cnt, ms = (C.c_int64 * 8)(), (C.c_double * 4)()
+        check(lib().ed_power_stats(self.handle, cnt, ms))
+        out = dict(zip(("n_samples", "n_exons", "n_jobs", "max_jobs", "n_skipped", "n_bad_samples", "largest_total", "map_words"), (int(v) for v in cnt)))
+        out.update(zip(("occupancy_ms", "walk_ms", "regions_ms", "exons_ms"), (float(v) for v in ms)))
+        return out
+
+    def free(self):
+        if self.handle:
+            lib().ed_power_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def region_runs(chromosome, start, end, regions):
+    """Coordinate regions to runs of exons.  chromosome, start, end: the exons in the plan's order (each chromosome one contiguous block;
+    the block's index is the plan's chromosome index); regions: (chromosome, start, end) triples.  A region's run goes from the first to
+    the last exon lying wholly inside it (start_i >= start and end_i <= end: TestCNV's rule); an exon between those two that is not
+    wholly inside belongs to the run as well -- a call cannot skip it.  Returns a CALL_DTYPE array (chrom, start_exon, end_exon, nexons =
+    the run's length); a region with no exon inside has start_exon = end_exon = -1 and nexons = 0 (chrom -1 when its chromosome has no
+    exon at all)."""
+    chromosome = np.asarray([str(c) for c in chromosome], dtype=object)
+    start, end = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+    if not (chromosome.size == start.size == end.size):
+        raise ValueError("chromosome, start and end must have one entry per exon")
+    blocks = {}
+    i, n = 0, int(chromosome.size)
+    while i < n:
+        j = i
+        while j < n and chromosome[j] == chromosome[i]:
+            j += 1
+        if chromosome[i] in blocks:
+            raise ValueError("the exons of chromosome %s are not one contiguous block" % chromosome[i])
+        blocks[chromosome[i]] = (len(blocks), i, j)
+        i = j
+    mono = {c: bool(np.all(np.diff(start[lo:hi]) >= 0) and np.all(np.diff(end[lo:hi]) >= 0)) for c, (_, lo, hi) in blocks.items()}
+    regions = list(regions)
+    out = np.zeros(len(regions), dtype=CALL_DTYPE)
+    out["chrom"], out["start_exon"], out["end_exon"] = -1, -1, -1
+    for r, (c, s, e) in enumerate(regions):
+        c = str(c)
+        if c not in blocks:
+            continue
+        k, lo, hi = blocks[c]
+        out["chrom"][r] = k
+        if mono[c]:
+            first = lo + int(np.searchsorted(start[lo:hi], s, "left"))
+            last = lo + int(np.searchsorted(end[lo:hi], e, "right")) - 1
+        else:
+            inside = np.flatnonzero((start[lo:hi] >= s) & (end[lo:hi] <= e))
+            first, last = (lo + int(inside[0]), lo + int(inside[-1])) if inside.size else (0, -1)
+        if first <= last:
+            out["start_exon"][r], out["end_exon"][r], out["nexons"][r] = first, last, last - first + 1
+    return out
+
+
+def detection_power(chrom_off, start, end, test, ref, phi, expected, rows, mixture=1.0, threshold=None, layout=0,
+                    transition_probability=1e-4, expected_CNV_length=50000.0, exons=False, device=0):
+    """Detection power of a cohort: PowerMap.regions(rows, threshold) of the samples' map on a plan of (chrom_off, start, end) with the
+    given transition parameters; with exons=True a pair (regions, PowerMap.exons()).  Arguments as Plan and Plan.power_map take them.
+    Answers, of a negative result: could a heterozygous deletion / duplication of this region have been seen in this sample at this depth?"""
+    plan = Plan(chrom_off, start, end, transition_probability, expected_CNV_length, device)
+    pm = None
+    try:
+        pm = plan.power_map(test, ref, phi, expected, mixture, layout)
+        reg = pm.regions(rows, threshold)
+        return (reg, pm.exons()) if exons else reg
+    finally:
+        if pm is not None:
+            pm.free()
+        plan.close()
+
+
 def chromosome_order(chromosome, start, end):
     """Return (order, chrom_levels, chrom_codes_sorted, chrom_off).  Levels are '1'..'22' first (those
     present), then the other names in first-seen order; exons are ordered by (level, midpoint) with
@@ -1706,6 +1925,35 @@ class ExomeDepth:
         order, _, _, chrom_off = chromosome_order(chromosome, start, end)
         return fit_prop_tumor(chrom_off, np.asarray(start)[order], np.asarray(end)[order], _as_r_integer(self.test[order]),
                               _as_r_integer(self.reference[order]), phi=self.phi[:1], expected=self.expected[:1], **options)
+
+    def detection_power(self, chromosome, start, end, regions=None, threshold=None, transition_probability=1e-4, expected_CNV_length=50000.0):
+        """Detection power of this sample at the object's phi, expected and prop_tumor (detection_power on one sample; not in the
+        reference): a POWER_DTYPE array, one row per region.  regions: (chromosome, start, end) coordinate triples, mapped to exon runs
+        by region_runs; None: the object's own CNV_calls (after CallCNVs, whose exon order the object then has), one row per call.
+        Exons are ordered as CallCNVs orders them; nothing of the object is changed."""
+        n = self.test.size
+        if not (len(start) == len(chromosome) == len(end) == n):
+            raise ValueError("The annotation vectors must have the same length as the data in the ExomeDepth x")
+        if self.phi.size == 0:
+            raise ValueError("the object has no fitted phi / expected (too few bins with reads)")
+        if not (np.all(self.phi == self.phi[0]) and np.all(self.expected == self.expected[0])):
+            raise NotImplementedError("detection_power with a per-exon phi or expected (phi.bins > 1, covariates) is not implemented: "
+                                      "there the value is no longer a function of the exon's total")
+        order, _, _, chrom_off = chromosome_order(chromosome, start, end)
+        s_start, s_end = np.asarray(start)[order], np.asarray(end)[order]
+        if regions is None:
+            if self.CNV_calls is None:
+                raise ValueError("regions=None needs the object's CNV_calls: run CallCNVs first")
+            rows = np.zeros(len(self.CNV_calls), dtype=CALL_DTYPE)
+            first = np.array([c["start.p"] - 1 for c in self.CNV_calls], dtype=np.int64)
+            rows["start_exon"], rows["end_exon"] = first, [c["end.p"] - 1 for c in self.CNV_calls]
+            rows["chrom"] = np.searchsorted(chrom_off, first, "right") - 1
+        else:
+            rows = region_runs(np.asarray([str(c) for c in chromosome], dtype=object)[order], s_start, s_end, regions)
+        out = detection_power(chrom_off, s_start, s_end, _as_r_integer(self.test[order]).reshape(n, 1),
+                              _as_r_integer(self.reference[order]).reshape(n, 1), self.phi[:1], self.expected[:1], rows, mixture=self.prop_tumor,
+                              threshold=threshold, transition_probability=transition_probability, expected_CNV_length=expected_CNV_length)
+        return out[:, 0]
 
     def AnnotateExtra(self, reference_annotation, min_overlap=0.5, column_name=None):
         """reference R/annotate_extra.R:41-73: adds `column_name` to every row of CNV_calls -- the `names` of the annotation's intervals the

@@ -54,6 +54,7 @@
 #include "ed_launch_plan.hpp"
 #include "ed_hmm_score.hpp"
 #include "ed_mix_plan.hpp"
+#include "ed_power_plan.hpp"
 
 using edown::DevBuf;
 using edown::PinBuf;
@@ -2943,3 +2944,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edscore.inc"
 #include "edbounds.inc"      // (reads edpost.inc's results) last: a kernel added at the end leaves every other symbol's code where it was (tools/isa_compare.py)
 #include "edmix.inc"         // (edpost.inc's lse3) behind it for the same reason
+#include "edpower.inc"       // (edrefset.inc's wave sum and scan) last again

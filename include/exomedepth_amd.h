@@ -377,6 +377,49 @@ int ed_plan_mixture_profile(const ed_plan* plan, const int32_t* d_test, const in
                             const double* d_phi, const double* d_expected, const double* d_grid, int n_grid, double* d_logev, void* stream);
 int ed_mix_geometry(int32_t out[4]);
 
+/* ---- the detection-power map: the expected Bayes factor of a CNV, per exon and per region ----
+ * What a missing call means: could a heterozygous deletion / duplication of this exon or region have been seen in this sample at this
+ * depth?  For sample s with (phi, expected, mixture), (a1_j, a2_j) the strict emissions' shape parameters of state j, and an exon
+ * whose total is n, with T = deletion or duplication:
+ *   X ~ BetaBinomial(n, a1_T, a2_T)     D_T(x) = log10(e) [e_T(x) - e_N(x)],  e_j(x) = lnbeta(a1_j + x, a2_j + n - x) - lnbeta(a1_j, a2_j)
+ *   mean_T = E[D_T(X)]  -- the exon's expected contribution to a call's BF when it truly is in state T (>= 0) --  var_T = Var[D_T(X)]
+ * Both are 0 for n = 0 and depend on the exon through n alone: the map walks every sample once per OCCUPIED total (a job), both
+ * alternatives in one pass, and every exon looks its total up.  A total above the largest one walked (ed_power_geometry; a sum of
+ * counts below 0 counts as such) is skipped: its exons read NaN and it is counted.  A sample whose six shape parameters are not all
+ * positive and finite (phi too large for the model) reads NaN everywhere and is counted; the other samples are not affected.
+ * The bits of a table value depend on (n, phi, expected, mixture) alone -- not on the number of samples, the other samples, the layout
+ * or the order of the jobs.
+ * ed_plan_power_map: test / ref are int32 counts, layout 0: [n_exons][n_samples], 1: [n_samples][n_exons], DEVICE arrays when
+ *   counts_on_device != 0, else HOST arrays; phi, expected and mixture_s are HOST double [n_samples]; mixture_s NULL: `mixture` for every
+ *   sample.  Complete on return (it waits for `stream`); the counts are not needed afterwards.  The plan must outlive the map.
+ *   ED_ERR_INVALID before anything is enqueued: a NULL pointer, a layout other than 0 / 1, n_samples outside 1 .. 2^20.
+ * ed_power_regions: rows are call rows of which chrom, start_exon and end_exon are read (a call table can be passed as it is): a run of
+ *   exons inside one chromosome of the plan, exon indices as in a call row.  HOST outputs: sums [4][n_rows][n_samples] (mean_del, var_del,
+ *   mean_dup, var_dup: the sums over the run's exons in a fixed order -- lane l of 64 adds exons first + l, first + 64 + l, ..., the lane
+ *   sums are folded 32, 16, .., 1 apart), n_empty [n_rows][n_samples] (exons of the run whose total is 0), price [n_rows], n_exons [n_rows].
+ *   price = log10(e) (sum over the gaps first .. last + 1 of lt[N->N] - (lt_first[N->T] + sum over the inner gaps of lt[T->T] +
+ *   lt_{last+1}[T->N])) from the plan's own table: the evidence at which Viterbi prefers exactly this segment over all normal between
+ *   normal flanks.  The bits of a row's values depend on its run and its sample alone.
+ *   ED_ERR_INVALID before anything is enqueued: a NULL pointer, n_rows < 0, a row with first > last, with a chromosome outside the plan,
+ *   outside its chromosome or across a chromosome boundary.
+ * ed_power_copy_exons: the per-exon map, HOST double [4][n_samples][n_exons].
+ * ed_power_copy_table: one sample's table: *n = its occupied totals; when cap >= *n also totals [*n] (ascending) and values [4][cap].
+ * ed_power_stats: counts = {samples, exons, jobs, most jobs of one sample, cells skipped, samples outside the model, largest total
+ *   walked in this map, 32-bit words of a row of the occupancy map}; ms (may be NULL) = {occupancy, walk, the kernels of the last
+ *   ed_power_regions, the kernels of the last ed_power_copy_exons}, host-timed between waits.
+ * ed_power_geometry: out = {values of x a walk takes per tile, occupancy cap (while every total is below it the narrow occupancy map is
+ *   used), the largest total that is walked, exons a region step takes} -- for tests that place their shapes on the edges. */
+typedef struct ed_power ed_power;
+int ed_plan_power_map(ed_power** map, const ed_plan* plan, const int32_t* test, const int32_t* ref, int counts_on_device, int layout,
+                      int64_t n_samples, const double* phi, const double* expected, const double* mixture_s, double mixture, void* stream);
+void ed_power_free(ed_power* map);
+int ed_power_regions(ed_power* map, const ed_call* rows, int64_t n_rows, double* sums, int32_t* n_empty, double* price, int32_t* n_exons,
+                     void* stream);
+int ed_power_copy_exons(ed_power* map, double* out, void* stream);
+int ed_power_copy_table(const ed_power* map, int64_t sample, int32_t* totals, double* values, int64_t cap, int64_t* n);
+int ed_power_stats(const ed_power* map, int64_t counts[8], double ms[4]);
+int ed_power_geometry(int32_t out[4]);
+
 /* ---- breakpoint credible intervals of call rows ----
  * Where does a call start and end, and how sure is that: from the posterior above, per call row of type T (1 deletion, 2 duplication).
  *   anchor a   the exon of the row, start_exon .. end_exon, with the largest log gamma(T); ties to the lowest index, NaN ignored
