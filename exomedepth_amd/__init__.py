@@ -10,7 +10,8 @@ from .api import (Batch, Cohort, MultiDevice, DeviceArray, device_count, PinnedA
                   Annotation, annotate_calls, cohort_call_recurrence, annot_geometry,
                   ReadCounter, getBamCounts, count_everted_reads, bed_targets, readcount_geometry,
                   CALL_BOUNDS_DTYPE,
-                  PowerMap, detection_power, region_runs, power_geometry, power_from_moments, POWER_DTYPE)
+                  PowerMap, detection_power, region_runs, power_geometry, power_from_moments, POWER_DTYPE,
+                  call_copy_number, copy_number_from_profile, ratio_geometry, CALL_DTYPE, COPY_RATIO_GRID)
 
 __all__ = ["Batch", "Cohort", "MultiDevice", "DeviceArray", "device_count", "PinnedArray", "ExomeDepth", "Plan", "Posterior", "fit_transitions", "fit_prop_tumor", "mixture_geometry", "EdError", "chromosome_order", "cohort_select_reference_sets", "refcohort_last_path", "fit_betabin", "fit_betabin_bins",
            "get_loglike_matrix", "get_power_betabinom", "refset_finalize", "select_reference_set", "somatic_CNV_call", "viterbi_hmm", "LIB_PATH",
@@ -18,4 +19,5 @@ __all__ = ["Batch", "Cohort", "MultiDevice", "DeviceArray", "device_count", "Pin
            "Annotation", "annotate_calls", "cohort_call_recurrence", "annot_geometry",
            "ReadCounter", "getBamCounts", "count_everted_reads", "bed_targets", "readcount_geometry",
            "CALL_BOUNDS_DTYPE",
-           "PowerMap", "detection_power", "region_runs", "power_geometry", "power_from_moments", "POWER_DTYPE"]
+           "PowerMap", "detection_power", "region_runs", "power_geometry", "power_from_moments", "POWER_DTYPE",
+           "call_copy_number", "copy_number_from_profile", "ratio_geometry", "CALL_DTYPE", "COPY_RATIO_GRID"]

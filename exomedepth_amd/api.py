@@ -294,6 +294,71 @@ class Plan:
                 if isinstance(d, DeviceArray):
                     d.free()
 
+    def ratio_profile(self, rows, test, ref, phi, expected, ratios, layout=0, stream=None, tail=False):
+        """The summed log-likelihood of every row's exons at every copy ratio of `ratios`, from the counts (include/exomedepth_amd.h:
+        ed_plan_ratio_profile): (L (n_rows, G), ratios_used (n_rows, G)).  rows: records with sample, chrom, start_exon, end_exon (global
+        0-based exon indices; Batch.calls(), or region_runs' rows with a `sample` field added).  test / ref: int32 counts, (n_exons, S)
+        with layout 0 or (S, n_exons) with layout 1; phi, expected: float64 (S,); host arrays, DeviceArrays or torch device tensors.
+        ratios: (G,), the same for every row, or (n_rows, G); 1 <= G <= 16.  A ratio r is evaluated at the dose mu = 2 (r - 1), and
+        ratios_used = 1 + mu / 2 is the ratio that dose stands for; a ratio outside (0, 2] (or NaN) reads NaN.
+        tail=True: (L, ratios_used, L_tail) -- L + L_tail is the double-double sum the kernel holds (ed_plan_ratio_profile_dd).  |L| is
+        hundreds of times the difference of two of a row's values, so take a difference as (L_a - L_b) + (tail_a - tail_b).
+
+        Genotyping known regions across a cohort needs nothing else:
+
+            runs = region_runs(chromosome, start, end, regions)                  # one exon run per region
+            runs = runs[runs["nexons"] > 0]
+            rows = np.zeros(len(runs) * S, dtype=CALL_DTYPE)                     # regions x samples
+            for k in ("chrom", "start_exon", "end_exon", "nexons"):
+                rows[k] = np.repeat(runs[k], S)
+            rows["sample"] = np.tile(np.arange(S), len(runs))
+            L, r = plan.ratio_profile(rows, test, ref, phi, expected, COPY_RATIO_GRID)
+            cn = copy_number_from_profile(r, L)["cn"].reshape(len(runs), S)"""
+        rows = _ratio_rows(rows)
+        n = int(rows.size)
+        if isinstance(phi, DeviceArray) and phi.shape is None:
+            S = phi.nbytes // 8
+        else:
+            S = int(np.size(phi)) if not _is_device(phi) else int(phi.shape[0])
+        ratios = np.asarray(ratios, dtype=np.float64)
+        if ratios.ndim == 1:
+            ratios = np.repeat(ratios[None, :], n, axis=0)
+        if ratios.ndim != 2 or ratios.shape[0] != n:
+            raise ValueError("ratios must have shape (G,) or (%d, G), got %s" % (n, ratios.shape))
+        doses = np.ascontiguousarray((2.0 * (ratios - 1.0)).T)
+        want = (self.n_exons, S) if not layout else (S, self.n_exons)
+        for x in (test, ref):
+            if not _is_device(x) and np.shape(x) != want:
+                raise ValueError("counts must have shape %s with layout %r, got %s" % (want, layout, np.shape(x)))
+        keep = []
+        try:
+            pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
+            pp, pe = _device_pointer(phi, np.float64, keep), _device_pointer(expected, np.float64, keep)
+            if tail:
+                L, T = self._ratio_doses(rows, pt, pr, pp, pe, S, doses, layout, stream, tail=True)
+                return np.ascontiguousarray(L.T), np.ascontiguousarray((1.0 + doses / 2.0).T), np.ascontiguousarray(T.T)
+            L = self._ratio_doses(rows, pt, pr, pp, pe, S, doses, layout, stream)
+            return np.ascontiguousarray(L.T), np.ascontiguousarray((1.0 + doses / 2.0).T)
+        finally:
+            for d in keep:
+                if isinstance(d, DeviceArray):
+                    d.free()
+
+    def _ratio_doses(self, rows, pt, pr, pp, pe, S, doses, layout=0, stream=None, tail=False):
+        """... on device pointers and doses (G, n_rows): L (G, n_rows); tail=True: (L, L_tail)"""
+        doses = np.ascontiguousarray(doses, dtype=np.float64)
+        G, n = doses.shape
+        out = np.empty((G, n), dtype=np.float64)
+        if tail:
+            rest = np.empty((G, n), dtype=np.float64)
+            check(lib().ed_plan_ratio_profile_dd(self.handle, _ptr(rows) if n else None, n, pt, pr, int(layout), int(S), pp, pe,
+                                                 _ptr(doses) if n else None, int(G), _ptr(out) if n else None, _ptr(rest) if n else None,
+                                                 C.c_void_p(stream or 0)))
+            return out, rest
+        check(lib().ed_plan_ratio_profile(self.handle, _ptr(rows) if n else None, n, pt, pr, int(layout), int(S), pp, pe,
+                                          _ptr(doses) if n else None, int(G), _ptr(out) if n else None, C.c_void_p(stream or 0)))
+        return out
+
     def power_map(self, test, ref, phi, expected, mixture=1.0, layout=0, stream=None):
         """The detection-power map of the samples (include/exomedepth_amd.h: ed_plan_power_map): a PowerMap.  test / ref: int32 counts,
         (n_exons, S) with layout 0 or (S, n_exons) with layout 1 -- host arrays, or both DeviceArrays / torch device tensors; phi, expected:
@@ -649,6 +714,44 @@ class Batch:
         """with enable_timing(): milliseconds of k_call_bounds in the last call_bounds() of this run (0: not timed)"""
         ms = C.c_float(0)
         check(lib().ed_batch_call_bounds_ms(self.handle, C.byref(ms)))
+        return float(ms.value)
+
+    def call_ratio_profile(self, ratios, tail=False):
+        """(L (n_calls, G), ratios_used (n_calls, G)): the copy-ratio profile of every call of the last run() (row i belongs to row i of
+        calls()), as Plan.ratio_profile on the run's own counts, phi and expected.  ratios: (G,) or (n_calls, G), 1 <= G <= 16.  Not
+        available after run_bins() / run_cov().  tail=True: (L, ratios_used, L_tail), L + L_tail the double-double sums: with ratios
+        (0.5, 1, 1.5), log10(e) ((L[:, k] - L[:, 1]) + (L_tail[:, k] - L_tail[:, 1])) at the call's type is call_info()'s BF_raw to a
+        few units in the last place, which the rounded values' difference alone is not (|L| is hundreds of times the difference)."""
+        n = self.n_calls()
+        ratios = np.asarray(ratios, dtype=np.float64)
+        if ratios.ndim == 1:
+            ratios = np.repeat(ratios[None, :], n, axis=0)
+        if ratios.ndim != 2 or ratios.shape[0] != n:
+            raise ValueError("ratios must have shape (G,) or (%d, G), got %s" % (n, ratios.shape))
+        doses = np.ascontiguousarray((2.0 * (ratios - 1.0)).T)
+        if tail:
+            L, T = self._call_ratio_doses(doses, tail=True)
+            return np.ascontiguousarray(L.T), np.ascontiguousarray((1.0 + doses / 2.0).T), np.ascontiguousarray(T.T)
+        L = self._call_ratio_doses(doses)
+        return np.ascontiguousarray(L.T), np.ascontiguousarray((1.0 + doses / 2.0).T)
+
+    def _call_ratio_doses(self, doses, tail=False):
+        """... on doses (G, n_calls): L (G, n_calls); tail=True: (L, L_tail)"""
+        doses = np.ascontiguousarray(doses, dtype=np.float64)
+        G, n = doses.shape
+        out = np.empty((G, n), dtype=np.float64)
+        if tail:
+            rest = np.empty((G, n), dtype=np.float64)
+            check(lib().ed_batch_copy_call_ratio_profile_dd(self.handle, _ptr(doses) if n else None, int(G), _ptr(out) if n else None,
+                                                            _ptr(rest) if n else None, n))
+            return out, rest
+        check(lib().ed_batch_copy_call_ratio_profile(self.handle, _ptr(doses) if n else None, int(G), _ptr(out) if n else None, n))
+        return out
+
+    def call_ratio_ms(self):
+        """with enable_timing(): milliseconds of the profile's kernels in the last call_ratio_profile() of this run (0: not timed)"""
+        ms = C.c_float(0)
+        check(lib().ed_batch_call_ratio_ms(self.handle, C.byref(ms)))
         return float(ms.value)
 
     def n_posterior_passes(self):
@@ -1471,6 +1574,202 @@ def fit_prop_tumor(chrom_off, start, end, tumor=None, normal=None, phi=None, exp
 
 
 # ---------------------------------------------------------------------------------------------
+# the copy number of a call: the likelihood profile over the copy ratio
+# ---------------------------------------------------------------------------------------------
+COPY_RATIOS = (0.5, 1.0, 1.5, 2.0)       # the copy ratios of CN 1 .. 4; CN 0 is evaluated at `ratio_floor`
+
+
+def ratio_geometry():
+    """{seg_tiles, narrow, max_grid, items_per_workgroup} of the copy-ratio profile's kernel (ed_ratio_geometry): a wavefront takes up to
+    seg_tiles tiles of 64 exons of a row; narrow = 0: there is no second mapping for short rows.  For tests placing rows on the edges."""
+    out = (C.c_int32 * 4)()
+    check(lib().ed_ratio_geometry(out))
+    return dict(zip(("seg_tiles", "narrow", "max_grid", "items_per_workgroup"), (int(v) for v in out)))
+
+
+def _ratio_rows(rows):
+    """rows as ed_call records: a CALL_DTYPE array as it is, else the fields sample, chrom, start_exon, end_exon of a structured array"""
+    rows = np.asarray(rows)
+    if rows.dtype == CALL_DTYPE:
+        return np.ascontiguousarray(rows).reshape(-1)
+    out = np.zeros(rows.size, dtype=CALL_DTYPE)
+    for k in ("sample", "chrom", "start_exon", "end_exon"):
+        out[k] = rows[k].reshape(-1)
+    out["nexons"] = out["end_exon"] - out["start_exon"] + 1
+    return out
+
+
+def _dose_grid(ratio_floor):
+    """the 16 doses of the first round: four from the floor to CN 1, then steps of 1/8 of a ratio up to CN 4; CN 0 .. 4 are the
+    indices 0, 3, 7, 11, 15"""
+    lo = 2.0 * (float(ratio_floor) - 1.0)
+    g = np.concatenate([lo + (-1.0 - lo) * np.arange(4) / 3.0, -1.0 + np.arange(1, 13) / 4.0])
+    g[0], g[3] = lo, -1.0
+    return g
+
+
+_CN_INDEX = (0, 3, 7, 11, 15)
+COPY_RATIO_GRID = tuple(float(1.0 + d / 2.0) for d in _dose_grid(0.05))     # that grid as ratios, at the default floor
+
+
+def _chi2_1(level):
+    """the `level` quantile of chi^2 with one degree of freedom"""
+    from statistics import NormalDist
+    if not 0.0 < level < 1.0:
+        raise ValueError("level must lie in (0, 1), got %r" % (level,))
+    return NormalDist().inv_cdf(0.5 + 0.5 * level) ** 2
+
+
+def copy_number_from_profile(ratios, L, ratio_floor=0.05):
+    """The evidence for the copy numbers 0 .. 4 of every row from its profile (pure numpy).  ratios (G,) or (n_rows, G), L (n_rows, G):
+    what Plan.ratio_profile / Batch.call_ratio_profile return.  Per row
+        log10_bf_cn[k] = log10(e) (L(r_k) - L(1)),  r = ratio_floor, 0.5, 1, 1.5, 2  for CN k = 0 .. 4
+    read at the columns whose ratio equals r_k (the first such column; NaN where the row was not evaluated there), and cn = the copy
+    number with the largest value, the first on ties, -1 where none is a number.  The model degenerates at ratio 0 (the expected
+    proportion goes to 0), so CN 0 is evaluated at `ratio_floor`: a modelling parameter that stands for the residual reads a homozygous
+    deletion still collects (mis-mapped reads, contamination), not a measured number.
+    Returns {"log10_bf_cn": (n_rows, 5), "cn": (n_rows,) int64, "ratios": the five ratios}."""
+    L = np.asarray(L, dtype=np.float64)
+    if L.ndim == 1:
+        L = L[None, :]
+    n, G = L.shape
+    ratios = np.asarray(ratios, dtype=np.float64)
+    if ratios.ndim == 1:
+        ratios = np.broadcast_to(ratios[None, :], (n, ratios.size))
+    if ratios.shape != (n, G):
+        raise ValueError("ratios must have shape (G,) or (n_rows, G) matching L %s, got %s" % (L.shape, ratios.shape))
+    want = np.array((float(ratio_floor),) + COPY_RATIOS)
+    at = np.full((n, 5), np.nan)
+    rows = np.arange(n)
+    used = 1.0 + (2.0 * (want - 1.0)) / 2.0                           # what ratio_profile reports for these ratios (the floor's last bit may differ)
+    for k in range(5):
+        hit = (ratios == want[k]) | (ratios == used[k])
+        col = np.argmax(hit, axis=1)                                  # the first column at that ratio
+        at[:, k] = np.where(hit.any(axis=1), L[rows, col] if G else np.nan, np.nan)
+    bf = np.log10(np.e) * (at - at[:, 2:3])
+    ranked = np.where(np.isnan(bf), -np.inf, bf)
+    cn = np.where(np.isnan(bf).all(axis=1), -1, np.argmax(ranked, axis=1)).astype(np.int64)
+    return {"log10_bf_cn": bf, "cn": cn, "ratios": want}
+
+
+def _ratio_search(evaluate, n_rows, rounds, level, ratio_floor):
+    """call_copy_number's search on `evaluate`: doses (G, n_rows) -> L (G, n_rows).  Pure numpy, vectorised over the rows."""
+    n = int(n_rows)
+    if rounds < 1 or not 0.0 < ratio_floor < 0.5:
+        raise ValueError("call_copy_number: rounds >= 1 and 0 < ratio_floor < 0.5 are needed")
+    q = _chi2_1(level)
+    cols = np.arange(n)
+    grid = np.repeat(_dose_grid(ratio_floor)[:, None], n, axis=1)
+    l = np.array(evaluate(grid), dtype=np.float64).reshape(MIX_GRID, n)
+    profile = l.copy()
+    trace = [{"grid": grid.copy(), "values": l.copy(), "k": _first_argmax(l)}]
+    for _ in range(1, int(rounds)):
+        k = trace[-1]["k"]
+        grid = _refine_grid(grid[np.maximum(k - 1, 0), cols], grid[np.minimum(k + 1, MIX_GRID - 1), cols])
+        l = np.array(evaluate(grid), dtype=np.float64).reshape(MIX_GRID, n)
+        trace.append({"grid": grid.copy(), "values": l.copy(), "k": _first_argmax(l)})
+    bad = np.zeros(n, dtype=bool)
+    for r in trace:
+        bad |= np.isnan(r["values"]).any(axis=0)
+    # the estimate: the vertex of the parabola through the last grid's largest value and its neighbours (the spacing of the first
+    # grid is not even, so the step is written for three abscissae)
+    k = trace[-1]["k"]
+    km, kp = np.maximum(k - 1, 0), np.minimum(k + 1, MIX_GRID - 1)
+    xk, lk = grid[k, cols], l[k, cols]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        h1, h2 = xk - grid[km, cols], grid[kp, cols] - xk
+        s1, s2 = (lk - l[km, cols]) / h1, (l[kp, cols] - lk) / h2
+        d2 = 2.0 * (s2 - s1) / (h1 + h2)
+        d1 = (s2 * h1 + s1 * h2) / (h1 + h2)
+        vertex = (k >= 1) & (k <= MIX_GRID - 2) & (d2 < 0.0)
+        m = np.where(vertex, np.clip(xk - d1 / d2, grid[km, cols], grid[kp, cols]), xk)
+        se = np.where(vertex, 1.0 / np.sqrt(-d2), np.nan)
+    # the profile-likelihood interval on every point evaluated: z = sqrt(2 (Lmax - L)) is linear where L is a parabola, so its crossing of
+    # sqrt(q) is interpolated linearly between the last point inside and the first outside, walking out from the largest value
+    x = np.concatenate([r["grid"] for r in trace], axis=0)
+    y = np.concatenate([r["values"] for r in trace], axis=0)
+    order = np.argsort(x, axis=0, kind="stable")
+    x, y = np.take_along_axis(x, order, axis=0), np.take_along_axis(y, order, axis=0)
+    top = _first_argmax(y)
+    lmax = y[top, cols] if n else np.zeros(0)
+    with np.errstate(invalid="ignore"):
+        z = np.sqrt(np.maximum(2.0 * (lmax[None, :] - y), 0.0))
+    zq = np.sqrt(q)
+    P = x.shape[0]
+    lo, hi = np.empty(n), np.empty(n)
+    for j in range(n):
+        t = int(top[j])
+        a = t
+        while a > 0 and z[a - 1, j] <= zq:
+            a -= 1
+        lo[j] = x[0, j] if a == 0 else x[a, j] - (x[a, j] - x[a - 1, j]) * (zq - z[a, j]) / (z[a - 1, j] - z[a, j])
+        b = t
+        while b < P - 1 and z[b + 1, j] <= zq:
+            b += 1
+        hi[j] = x[P - 1, j] if b == P - 1 else x[b, j] + (x[b + 1, j] - x[b, j]) * (zq - z[b, j]) / (z[b + 1, j] - z[b, j])
+    ratios0 = 1.0 + trace[0]["grid"].T / 2.0
+    cnp = copy_number_from_profile(ratios0, profile.T, ratios0[0, 0] if n else ratio_floor)
+    cn_l = profile[list(_CN_INDEX), :]
+    with np.errstate(invalid="ignore"):
+        gain = 2.0 * (lmax - np.max(cn_l, axis=0)) if n else np.zeros(0)
+        informative = ~bad & (2.0 * (np.max(profile, axis=0) - np.min(profile, axis=0)) >= q) if n else np.zeros(0, dtype=bool)
+    nan = np.full(n, np.nan)
+    floor_dose = _dose_grid(ratio_floor)[0]
+
+    def as_ratio(d):                       # the floor's dose stands for ratio_floor itself (1 + dose / 2 may differ from it in the last bit)
+        return np.where(bad, nan, np.where(d == floor_dose, float(ratio_floor), 1.0 + d / 2.0))
+    return {"ratio": as_ratio(m), "ratio_se": np.where(bad, nan, se / 2.0), "ratio_lo": as_ratio(lo), "ratio_hi": as_ratio(hi),
+            "cn": np.where(bad, -1, cnp["cn"]), "log10_bf_cn": np.where(bad[:, None], np.nan, cnp["log10_bf_cn"]),
+            "mosaic_gain": np.where(bad, nan, gain), "informative": informative, "log_likelihood": np.where(bad, nan, lmax),
+            "profile": profile, "evaluations": len(trace), "trace": trace}
+
+
+def call_copy_number(chrom_off, start, end, rows, test=None, ref=None, phi=None, expected=None, rounds=3, level=0.95, ratio_floor=0.05,
+                     evaluate=None, layout=0, device=0):
+    """How many copies is a call?  Per row (sample, first exon .. last exon) the maximum-likelihood copy ratio of its exons with a
+    profile-likelihood interval, the evidence for the copy numbers 0 .. 4 and a test of whether any of them fits (not in the reference,
+    whose advice is to look at reads.ratio).  The objective is Plan.ratio_profile's L(row, ratio): the beta-binomial emission of the HMM
+    at any copy ratio instead of the three the states stand for.
+
+    rows: records with sample, chrom, start_exon, end_exon -- a call table (Batch.calls()) or regions crossed with samples.  test,
+    ref: counts (n_exons, S), or (S, n_exons) with layout=1; phi, expected: one value per sample.  evaluate: a callable doses
+    (G, n_rows) -> L (G, n_rows) that stands for the device (dose = 2 (ratio - 1)).
+
+    The search is deterministic and runs in numpy.  Round 1 evaluates a fixed grid of 16 ratios from ratio_floor to 2 that holds the
+    ratios of CN 0 .. 4 (ratio_floor, 0.5, 1, 1.5, 2); every later round takes the first index k* of the row's largest value, brackets
+    the two neighbours and evaluates 16 equally spaced ratios with both ends.  Per row:
+      ratio        the vertex of the parabola through k* - 1, k*, k* + 1 of the last grid, clamped to the bracket (the grid point itself
+                   where k* is the grid's end or the points are not concave)
+      ratio_se     from the parabola's curvature, 1 / sqrt(-L''); NaN without a vertex
+      ratio_lo, ratio_hi   where 2 (Lmax - L) crosses the chi^2_1 quantile of `level`, Lmax the largest value evaluated; interpolated
+                   (linearly in the square root of that deviance) on all points evaluated, the grid's end where it is never crossed
+      cn, log10_bf_cn      copy_number_from_profile on round 1
+      mosaic_gain  2 (Lmax - the largest L at the five copy numbers): chi^2_1 under "the copy ratio is one of them"; large for a mosaic
+                   or subclonal event
+      informative  False where the profile's range over round 1, 2 (max - min), stays below the quantile: the row says nothing
+    and log_likelihood (Lmax), profile (round 1, (16, n_rows)), evaluations, trace.  A row with a NaN at any ratio evaluated reads NaN,
+    cn -1, and is not informative; the other rows are not affected."""
+    rows = _ratio_rows(rows)
+    n = int(rows.size)
+    if evaluate is not None:
+        return _ratio_search(evaluate, n, rounds, level, ratio_floor)
+    if test is None or ref is None or phi is None or expected is None:
+        raise ValueError("call_copy_number: counts, phi and expected (or `evaluate`) are needed")
+    plan = Plan(chrom_off, start, end, device=device)
+    keep = []
+    try:
+        S = int(np.size(phi)) if not _is_device(phi) else int(phi.shape[0])
+        pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
+        pp, pe = _device_pointer(phi, np.float64, keep), _device_pointer(expected, np.float64, keep)
+        return _ratio_search(lambda doses: plan._ratio_doses(rows, pt, pr, pp, pe, S, doses, layout), n, rounds, level, ratio_floor)
+    finally:
+        for d in keep:
+            if isinstance(d, DeviceArray):
+                d.free()
+        plan.close()
+
+
+# ---------------------------------------------------------------------------------------------
 # detection power: the expected Bayes factor of a CNV per exon and per region
 # ---------------------------------------------------------------------------------------------
 POWER_DTYPE = np.dtype([("chrom", "<i4"), ("first_exon", "<i4"), ("last_exon", "<i4"), ("n_exons", "<i4"), ("n_empty", "<i4"),
@@ -1777,7 +2076,8 @@ class ExomeDepth:
         col = 0 if type == "deletion" else 2
         return float(np.sum(self.likelihood[which, col] - self.likelihood[which, 1]))
 
-    def CallCNVs(self, chromosome, start, end, name, transition_probability=1e-4, expected_CNV_length=50000, posterior=False, breakpoints=False):
+    def CallCNVs(self, chromosome, start, end, name, transition_probability=1e-4, expected_CNV_length=50000, posterior=False, breakpoints=False,
+                 copy_number=False):
         """reference R/class_definition.R:311-419: order exons, one Viterbi chain per chromosome,
         call table with start.p/end.p (1-based, global), type, nexons, start, end, chromosome, id.
 
@@ -1795,7 +2095,13 @@ class ExomeDepth:
         of the call's two breakpoints from the same posterior (Batch.call_bounds).  start.p.lo <= start.p.hi <= end.p.lo <= end.p.hi are
         exon positions, 1-based like start.p; start.lo / start.hi are those exons' start coordinates, end.lo / end.hi their end
         coordinates; start.keep / end.keep the probability that the run of the call's state through its best-supported exon reaches at
-        least the call's own first / last exon.  A call that cannot be walked keeps its own positions and NaN."""
+        least the call's own first / last exon.  A call that cannot be walked keeps its own positions and NaN.
+
+        copy_number=True appends six columns from the call's likelihood profile over the copy ratio (call_copy_number with its defaults,
+        on the run's own counts): copy.ratio, the maximum-likelihood copy ratio, with its 95 % profile-likelihood interval copy.ratio.lo /
+        copy.ratio.hi; copy.number, the best of CN 0 .. 4; BF.copy.number, the log10 Bayes factor of that copy number against the
+        runner-up; mosaic.gain, twice the log-likelihood the free ratio gains over the best copy number (chi^2_1 when the call has an
+        integer copy number).  Needs one (phi, expected) for the sample: not available with phi.bins > 1 or covariates."""
         if breakpoints is None or isinstance(breakpoints, (bool, np.bool_)):
             level = 0.95 if breakpoints else None
         else:
@@ -1822,6 +2128,9 @@ class ExomeDepth:
         self.annotations = {"name": name, "chromosome": chrom_sorted, "start": start, "end": end}
         self.cor_test_reference = float(np.corrcoef(self.test, self.reference)[0, 1])
         constant = bool(np.all(self.phi == self.phi[0]) and np.all(self.expected == self.expected[0]))
+        if copy_number and not constant:
+            raise NotImplementedError("copy_number=True needs one (phi, expected) for the sample: phi.bins > 1 and covariates are not served")
+        ccn = None
         if constant:
             plan = Plan(chrom_off, start, end, transition_probability, expected_CNV_length)
             batch = Batch(plan, 1)
@@ -1834,6 +2143,8 @@ class ExomeDepth:
                 self.Viterbi_path = batch.path()[:, 0].astype(np.int64)
                 cpost = batch.call_posterior() if posterior else None
                 cbnd = batch.call_bounds(level) if level is not None else None
+                if copy_number and len(raw):
+                    ccn = _ratio_search(batch._call_ratio_doses, len(raw), 3, 0.95, 0.05)
             finally:
                 batch.close()
                 plan.close()
@@ -1896,6 +2207,12 @@ class ExomeDepth:
                 calls[-1].update({"start.p.lo": slo + 1, "start.p.hi": shi + 1, "end.p.lo": elo + 1, "end.p.hi": ehi + 1,
                                   "start.lo": int(start[slo]), "start.hi": int(start[shi]), "end.lo": int(end[elo]), "end.hi": int(end[ehi]),
                                   "start.keep": float(np.exp(q["log_keep_start"])), "end.keep": float(np.exp(q["log_keep_end"]))})
+            if ccn is not None:
+                i = len(calls) - 1
+                bf = np.sort(ccn["log10_bf_cn"][i])          # (a NaN row stays NaN throughout)
+                calls[-1].update({"copy.ratio": float(ccn["ratio"][i]), "copy.ratio.lo": float(ccn["ratio_lo"][i]),
+                                  "copy.ratio.hi": float(ccn["ratio_hi"][i]), "copy.number": int(ccn["cn"][i]),
+                                  "BF.copy.number": float(bf[-1] - bf[-2]), "mosaic.gain": float(ccn["mosaic_gain"][i])})
         self.CNV_calls = calls
         return self
 

@@ -55,6 +55,7 @@
 #include "ed_hmm_score.hpp"
 #include "ed_mix_plan.hpp"
 #include "ed_power_plan.hpp"
+#include "ed_ratio_plan.hpp"
 
 using edown::DevBuf;
 using edown::PinBuf;
@@ -1415,6 +1416,8 @@ struct ed_batch {
   const int32_t* last_test = nullptr;   // inputs of the last ed_batch_run (for ed_batch_copy_call_info)
   const int32_t* last_ref = nullptr;
   const double* last_expected = nullptr;
+  const double* last_phi = nullptr;     // ... its dispersions (edratio.inc); per sample only where last_plain
+  bool last_plain = true;               // the last run was ed_batch_run: neither depth-binned nor covariate
   const double* last_cov_X = nullptr;   // covariate model of the last run (edcov.inc): expected is per exon
   const double* last_cov_beta = nullptr;
   int last_cov_K = -1;
@@ -1434,6 +1437,8 @@ struct ed_batch {
   DevBuf<ed_call_bounds> d_cbounds;  // per-call breakpoint intervals (edbounds.inc), grow-only (as d_cpost)
   Event bounds_ev[2];        // with `timing`: around k_call_bounds; made on first use
   int64_t bounds_stamp = -1; // post_passes at the last timed k_call_bounds (its events belong to that posterior)
+  Event ratio_ev[2];         // with `timing`: around k_ratio_profile / k_ratio_sum (edratio.inc); made on first use
+  bool ratio_timed = false;  // they hold the last profile request of the last run; a run clears it
   bool fused = false;        // run emissions + Viterbi as ONE kernel (edfused.inc) instead of two overlapped ones
   bool keep_loglik = true;   // fused mode only: also write the [E][3][S] likelihood matrix (the S4 `likelihood` slot)
   int fit_hist = 1;          // ed_batch_fit: 1 = iterate on count histograms (one pass over the counts), geometry picked from
@@ -2206,6 +2211,7 @@ static int run_open(Run& r, ed_batch* b, const int32_t* d_test, const int32_t* d
   b->stream = r.tail;
   b->split_recorded = false;
   b->last_test = d_test; b->last_ref = d_ref; b->last_expected = d_expected; b->last_layout = b->counts_layout; b->last_cb = r.cb;
+  b->last_phi = d_phi; b->last_plain = r.plain; b->ratio_timed = false;
   b->last_cov_X = em.cov ? em.X : nullptr; b->last_cov_K = em.cov ? em.K : -1; b->last_cov_beta = em.cov ? em.beta : nullptr;
   return ED_OK;
 }
@@ -2945,3 +2951,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edbounds.inc"      // (reads edpost.inc's results) last: a kernel added at the end leaves every other symbol's code where it was (tools/isa_compare.py)
 #include "edmix.inc"         // (edpost.inc's lse3) behind it for the same reason
 #include "edpower.inc"       // (edrefset.inc's wave sum and scan) last again
+#include "edratio.inc"       // (the call decoration's dd_add) and again

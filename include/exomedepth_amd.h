@@ -420,6 +420,52 @@ int ed_power_copy_table(const ed_power* map, int64_t sample, int32_t* totals, do
 int ed_power_stats(const ed_power* map, int64_t counts[8], double ms[4]);
 int ed_power_geometry(int32_t out[4]);
 
+/* ---- the copy-ratio profile: how many copies is a call? ----
+ * The HMM's states stand for the copy ratios 0.5, 1 and 1.5; the beta-binomial emission is defined for any.  For a row (sample s, exons
+ * start_exon .. end_exon, global indices as in ed_call) and a DOSE mu, -2 < mu <= 2 -- the copy ratio is r = 1 + mu / 2 --
+ *   L(row, mu) = sum over the row's exons of  lnbeta(a1 + obs_i, (a2 + tot_i) - obs_i) - lnbeta(a1, a2)
+ *   (a1, a2) = shape_params(ep, sd),  sd = sqrt((phi_s e_s)(1 - e_s)),  ep = the deletion proportion at mixture |mu| (mu < 0), e_s (mu = 0),
+ *   the duplication proportion at mixture |mu| (mu > 0)
+ * -- the strict emissions, operation for operation: a term has the bits of the likelihood matrix of a strict run at mixture |mu| in the
+ * deletion / normal / duplication column.  The terms are added as a double-double in one fixed order per row and rounded once.  Its
+ * maximiser over mu estimates the row's copy ratio, its values at mu = -2 + (a floor), -1, 0, 1, 2 compare the copy numbers 0 .. 4
+ * (copy_number_from_profile / call_copy_number in the Python package).
+ *   rows     HOST ed_call [n_rows]; sample, chrom, start_exon, end_exon are read (type and nexons are not): sample < n_samples, start <= end,
+ *            both inside the chromosome
+ *   d_test, d_ref  DEVICE int32 counts; layout 0: [n_exons][n_samples], 1: [n_samples][n_exons]
+ *   d_phi, d_expected  DEVICE double [n_samples]
+ *   grid     HOST double [G][n_rows]: every row has its own doses; 1 <= G <= 16
+ *   out      HOST double [G][n_rows]
+ * The entry enqueues on `stream`, waits and writes `out`.  A dose that is NaN, <= -2 or > 2 gives NaN at that (row, grid point) and
+ * changes nothing else; where a shape parameter is not positive (a small ratio with a large phi) the value is what the strict arithmetic
+ * gives, NaN for NaN.  The bits of a value depend on the row's counts, phi_s, e_s and mu alone -- not on the other rows, their order,
+ * n_samples, G, the grid point's index or the layout.
+ * ED_ERR_INVALID before anything is enqueued: G outside 1 .. 16, a NULL plan, a layout other than 0 / 1, n_samples outside 1 .. 2^20, a
+ * row outside its chromosome or the samples, a NULL array with n_rows > 0.  n_rows = 0 is a success that does nothing.
+ * ed_batch_copy_call_ratio_profile: the same for the call table of the batch's last ed_batch_run -- row i is call i of
+ *   ed_batch_copy_calls; grid and host_out are [G][n_calls] and cap >= n_calls says that they are.  Counts, phi and expected are the
+ *   run's inputs, which must still be what the run was given (as for ed_batch_copy_call_info); the batch's mixtures do not enter: the
+ *   profile is in observed ratio.  ED_ERR_STATE after ed_batch_run_bins / ed_batch_run_cov, whose models have no single (phi, expected)
+ *   per sample; nothing is enqueued.
+ * ed_plan_ratio_profile_dd / ed_batch_copy_call_ratio_profile_dd: the same values, and beside each the remainder of its rounding, out_tail /
+ *   host_tail HOST double [G][n_rows]: out + out_tail is the double-double sum (|out_tail| <= half a unit in out's last place; 0 beside a
+ *   value that is not finite).  |L| is hundreds of times the difference of two profiles of a row, so the difference of two rounded values
+ *   has lost that many bits; (out_a - out_b) + (tail_a - tail_b) has not -- it is the call decoration's Bayes factor to a few units in
+ *   the last place.  The tails obey the same invariance as the values.
+ * ed_batch_call_ratio_ms: with ed_batch_enable_timing, the milliseconds of the two kernels of the last such request of this run (0: not timed).
+ * ed_ratio_geometry: out = {tiles of 64 exons of a segment (a wavefront's share of a row), the row length up to which the narrow mapping is
+ *   taken (0: there is none), the largest G, items a workgroup serves} -- for tests that place their rows on the edges. */
+int ed_plan_ratio_profile(const ed_plan* plan, const ed_call* rows, int64_t n_rows, const int32_t* d_test, const int32_t* d_ref, int layout,
+                          int64_t n_samples, const double* d_phi, const double* d_expected, const double* grid, int G, double* out,
+                          void* stream);
+int ed_plan_ratio_profile_dd(const ed_plan* plan, const ed_call* rows, int64_t n_rows, const int32_t* d_test, const int32_t* d_ref, int layout,
+                             int64_t n_samples, const double* d_phi, const double* d_expected, const double* grid, int G, double* out,
+                             double* out_tail, void* stream);
+int ed_batch_copy_call_ratio_profile(ed_batch* batch, const double* grid, int G, double* host_out, int64_t cap);
+int ed_batch_copy_call_ratio_profile_dd(ed_batch* batch, const double* grid, int G, double* host_out, double* host_tail, int64_t cap);
+int ed_batch_call_ratio_ms(ed_batch* batch, float* ms);
+int ed_ratio_geometry(int32_t out[4]);
+
 /* ---- breakpoint credible intervals of call rows ----
  * Where does a call start and end, and how sure is that: from the posterior above, per call row of type T (1 deletion, 2 duplication).
  *   anchor a   the exon of the row, start_exon .. end_exon, with the largest log gamma(T); ties to the lowest index, NaN ignored
