@@ -14,6 +14,7 @@ read like the reference's own examples:
 All arithmetic of the path runs on the GPU; this module only marshals buffers (numpy on the host,
 optionally torch CUDA tensors for device-resident inputs).
 """
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -184,6 +185,32 @@ def _is_device(x):
     return isinstance(x, (DeviceArray, _RawDevice)) or (hasattr(x, "data_ptr") and getattr(x, "is_cuda", False))
 
 
+@contextlib.contextmanager
+def _staged():
+    """the `keep` list of one call: what _device_pointer uploads for it, and any DeviceArray the call appends itself, is freed on the way out"""
+    keep = []
+    try:
+        yield keep
+    finally:
+        for d in keep:
+            if isinstance(d, DeviceArray):
+                d.free()
+
+
+def _n_samples_of(phi):
+    """the number of samples, from the per-sample dispersions: host data, a DeviceArray or a torch device tensor"""
+    if isinstance(phi, DeviceArray) and phi.shape is None:
+        return phi.nbytes // 8
+    return int(np.size(phi)) if not _is_device(phi) else int(phi.shape[0])
+
+
+def _check_counts_shape(x, n_exons, S, layout):
+    """a host count matrix is (n_exons, S) with layout 0, (S, n_exons) with layout 1; a device array is taken as it is"""
+    want = (n_exons, S) if not layout else (S, n_exons)
+    if not _is_device(x) and np.shape(x) != want:
+        raise ValueError("counts must have shape %s with layout %r, got %s" % (want, layout, np.shape(x)))
+
+
 def _per_sample_mixture(mixture, n, device_ok=False):
     """None for a scalar mixture (today's path); otherwise the per-sample form: a float64[n] host array, checked here (one finite value
     per sample) before any device work -- or, with device_ok, a device array passed through as it is"""
@@ -228,16 +255,11 @@ class Plan:
         S, E = int(n_samples), self.n_exons
         if not _is_device(loglik) and np.shape(loglik) != (E, 3, S):
             raise ValueError("loglik must have shape (%d, 3, %d), got %s" % (E, S, np.shape(loglik)))
-        keep = []
-        ll = _device_pointer(loglik, np.float64, keep)
-        work = DeviceArray(nbytes=E * 3 * S * 8)
-        try:
+        with _staged() as keep:
+            ll = _device_pointer(loglik, np.float64, keep)
+            work = DeviceArray(nbytes=E * 3 * S * 8)
+            keep.append(work)
             return self._transition_score(ll, S, work, stream)
-        finally:
-            work.free()
-            for d in keep:
-                if isinstance(d, DeviceArray):
-                    d.free()
 
     def _transition_score(self, ll, S, work, stream=None):
         """... on a device pointer, with the caller's work array (n_exons * 3 * S doubles)"""
@@ -260,10 +282,7 @@ class Plan:
         ed_plan_mixture_profile): (G, n_chrom, S) float64.  test / ref: int32 counts of the tumours and their normals, (n_exons, S) with
         layout 0 or (S, n_exons) with layout 1; phi, expected: float64 (S,); host arrays, DeviceArrays or torch device tensors.  grid:
         (G, S), every pair its own mixtures, or (G,), the same for every pair; 1 <= G <= 16."""
-        if isinstance(phi, DeviceArray) and phi.shape is None:
-            S = phi.nbytes // 8
-        else:
-            S = int(np.size(phi)) if not _is_device(phi) else int(phi.shape[0])
+        S = _n_samples_of(phi)
         if _is_device(grid):
             G = int(grid.shape[0])
             if tuple(grid.shape) != (G, S):
@@ -275,24 +294,17 @@ class Plan:
             if grid.ndim != 2 or grid.shape[1] != S:
                 raise ValueError("grid must have shape (G, %d) or (G,), got %s" % (S, grid.shape))
             G = int(grid.shape[0])
-        want = (self.n_exons, S) if not layout else (S, self.n_exons)
         for x in (test, ref):
-            if not _is_device(x) and np.shape(x) != want:
-                raise ValueError("counts must have shape %s with layout %r, got %s" % (want, layout, np.shape(x)))
-        keep = []
-        out = DeviceArray(nbytes=max(G, 1) * self.n_chrom * S * 8)
-        try:
+            _check_counts_shape(x, self.n_exons, S, layout)
+        with _staged() as keep:
+            out = DeviceArray(nbytes=max(G, 1) * self.n_chrom * S * 8)
+            keep.append(out)
             pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
             pp, pe = _device_pointer(phi, np.float64, keep), _device_pointer(expected, np.float64, keep)
             pg = _device_pointer(grid, np.float64, keep)
             check(lib().ed_plan_mixture_profile(self.handle, pt, pr, int(layout), S, pp, pe, pg, G, out.ptr, C.c_void_p(stream or 0)))
             check(lib().ed_synchronize(C.c_void_p(stream or 0)))
             return out.to_host(np.float64, (G, self.n_chrom, S))
-        finally:
-            out.free()
-            for d in keep:
-                if isinstance(d, DeviceArray):
-                    d.free()
 
     def ratio_profile(self, rows, test, ref, phi, expected, ratios, layout=0, stream=None, tail=False):
         """The summed log-likelihood of every row's exons at every copy ratio of `ratios`, from the counts (include/exomedepth_amd.h:
@@ -316,22 +328,16 @@ class Plan:
             cn = copy_number_from_profile(r, L)["cn"].reshape(len(runs), S)"""
         rows = _ratio_rows(rows)
         n = int(rows.size)
-        if isinstance(phi, DeviceArray) and phi.shape is None:
-            S = phi.nbytes // 8
-        else:
-            S = int(np.size(phi)) if not _is_device(phi) else int(phi.shape[0])
+        S = _n_samples_of(phi)
         ratios = np.asarray(ratios, dtype=np.float64)
         if ratios.ndim == 1:
             ratios = np.repeat(ratios[None, :], n, axis=0)
         if ratios.ndim != 2 or ratios.shape[0] != n:
             raise ValueError("ratios must have shape (G,) or (%d, G), got %s" % (n, ratios.shape))
         doses = np.ascontiguousarray((2.0 * (ratios - 1.0)).T)
-        want = (self.n_exons, S) if not layout else (S, self.n_exons)
         for x in (test, ref):
-            if not _is_device(x) and np.shape(x) != want:
-                raise ValueError("counts must have shape %s with layout %r, got %s" % (want, layout, np.shape(x)))
-        keep = []
-        try:
+            _check_counts_shape(x, self.n_exons, S, layout)
+        with _staged() as keep:
             pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
             pp, pe = _device_pointer(phi, np.float64, keep), _device_pointer(expected, np.float64, keep)
             if tail:
@@ -339,10 +345,6 @@ class Plan:
                 return np.ascontiguousarray(L.T), np.ascontiguousarray((1.0 + doses / 2.0).T), np.ascontiguousarray(T.T)
             L = self._ratio_doses(rows, pt, pr, pp, pe, S, doses, layout, stream)
             return np.ascontiguousarray(L.T), np.ascontiguousarray((1.0 + doses / 2.0).T)
-        finally:
-            for d in keep:
-                if isinstance(d, DeviceArray):
-                    d.free()
 
     def _ratio_doses(self, rows, pt, pr, pp, pe, S, doses, layout=0, stream=None, tail=False):
         """... on device pointers and doses (G, n_rows): L (G, n_rows); tail=True: (L, L_tail)"""
@@ -1756,16 +1758,13 @@ def call_copy_number(chrom_off, start, end, rows, test=None, ref=None, phi=None,
     if test is None or ref is None or phi is None or expected is None:
         raise ValueError("call_copy_number: counts, phi and expected (or `evaluate`) are needed")
     plan = Plan(chrom_off, start, end, device=device)
-    keep = []
     try:
-        S = int(np.size(phi)) if not _is_device(phi) else int(phi.shape[0])
-        pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
-        pp, pe = _device_pointer(phi, np.float64, keep), _device_pointer(expected, np.float64, keep)
-        return _ratio_search(lambda doses: plan._ratio_doses(rows, pt, pr, pp, pe, S, doses, layout), n, rounds, level, ratio_floor)
+        with _staged() as keep:
+            S = _n_samples_of(phi)
+            pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
+            pp, pe = _device_pointer(phi, np.float64, keep), _device_pointer(expected, np.float64, keep)
+            return _ratio_search(lambda doses: plan._ratio_doses(rows, pt, pr, pp, pe, S, doses, layout), n, rounds, level, ratio_floor)
     finally:
-        for d in keep:
-            if isinstance(d, DeviceArray):
-                d.free()
         plan.close()
 
 
@@ -1832,7 +1831,7 @@ class PowerMap:
     def __init__(self, plan, test, ref, phi, expected, mixture=1.0, layout=0, stream=None):
         self.plan, self.stream = plan, stream
         phi, expected = _f64(np.atleast_1d(phi)), _f64(np.atleast_1d(expected))
-        S = int(phi.size)
+        S = _n_samples_of(phi)
         if expected.size != S:
             raise ValueError("phi and expected must have one value per sample")
         self.n_samples = S
@@ -1840,20 +1839,18 @@ class PowerMap:
         on_dev = _is_device(test) and _is_device(ref)
         if not on_dev and (_is_device(test) or _is_device(ref)):
             raise ValueError("test and ref must both be device arrays or both be host arrays")
-        want = (plan.n_exons, S) if not layout else (S, plan.n_exons)
-        keep = []
-        if on_dev:
-            pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
-        else:
-            test, ref = _i32(test), _i32(ref)
-            for x in (test, ref):
-                if x.shape != want:
-                    raise ValueError("counts must have shape %s with layout %r, got %s" % (want, layout, x.shape))
-            pt, pr = _ptr(test), _ptr(ref)
         self.handle = C.c_void_p()
-        check(lib().ed_plan_power_map(C.byref(self.handle), plan.handle, pt, pr, int(on_dev), int(layout), S, _ptr(phi), _ptr(expected),
-                                      _ptr(mix) if mix is not None else None, 1.0 if mix is not None else float(mixture),
-                                      C.c_void_p(stream or 0)))
+        with _staged() as keep:
+            if on_dev:
+                pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
+            else:
+                test, ref = _i32(test), _i32(ref)
+                for x in (test, ref):
+                    _check_counts_shape(x, plan.n_exons, S, layout)
+                pt, pr = _ptr(test), _ptr(ref)
+            check(lib().ed_plan_power_map(C.byref(self.handle), plan.handle, pt, pr, int(on_dev), int(layout), S, _ptr(phi), _ptr(expected),
+                                          _ptr(mix) if mix is not None else None, 1.0 if mix is not None else float(mixture),
+                                          C.c_void_p(stream or 0)))
 
     def regions(self, rows, threshold=None):
         """Per (region, sample): a POWER_DTYPE array of shape (n_regions, n_samples).  rows: a call table (CALL_DTYPE; chrom, start_exon

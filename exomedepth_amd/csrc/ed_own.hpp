@@ -84,6 +84,23 @@ public:
   explicit operator bool() const { return e_ != nullptr; }
 };
 
+// N events made on first use, and whether they hold something: `live` is set by whoever recorded all of them and cleared (drop) by
+// whatever makes their times stale.  The events themselves are kept from one use to the next.
+template <int N>
+struct EventSet {
+  Event ev[N];
+  bool live = false;
+  hipError_t ready()
+  {
+    hipError_t rc = hipSuccess;
+    for (auto& e : ev) { if (!e && rc == hipSuccess) rc = e.create(); }
+    return rc;
+  }
+  hipError_t record(int i, hipStream_t st) { return hipEventRecord(ev[i], st); }
+  hipError_t elapsed(int i, int j, float* ms) const { return hipEventElapsedTime(ms, ev[i], ev[j]); }
+  void drop() { live = false; }
+};
+
 // destroys without synchronising (the runtime lets queued work finish)
 class Stream {
   hipStream_t s_ = nullptr;

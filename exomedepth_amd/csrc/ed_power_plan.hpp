@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <numeric>
 #include <vector>
+#include "ed_rows.hpp"
 
 namespace edpower {
 
@@ -78,15 +79,7 @@ inline double region_sum(int64_t n, F at)
   return p[0];
 }
 
-// a region row against the plan: 0 fine, 1 first > last, 2 chromosome out of range, 3 not inside its chromosome (an exon outside the plan,
-// or a run that crosses a chromosome boundary)
-inline int row_fault(int32_t chrom, int32_t first, int32_t last, int32_t C, const int32_t* chrom_off)
-{
-  if (chrom < 0 || chrom >= C) return 2;
-  if (first > last) return 1;
-  if (first < chrom_off[chrom] || last >= chrom_off[chrom + 1]) return 3;
-  return 0;
-}
+using edrows::row_fault;     // a region row against the plan: the region form (ed_rows.hpp)
 
 // the rows of the plan's table a region's price reads, for the run first .. last (exon indices of the plan) of chromosome c: the row of
 // the gap in front of exon e is c + e (every chromosome before it has one closing gap more than exons).  N->N and N->T are constants,

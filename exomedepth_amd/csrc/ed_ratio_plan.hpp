@@ -14,6 +14,7 @@
 
 #include <cstdint>
 #include <vector>
+#include "ed_rows.hpp"
 
 namespace edratio {
 
@@ -53,15 +54,7 @@ struct Items {
   int64_t n_slots = 0;
 };
 
-// a row against the design: 0 fine, 1 first > last, 2 chromosome out of range, 3 not inside its chromosome, 4 sample out of range
-inline int row_fault(int32_t sample, int32_t chrom, int32_t first, int32_t last, int64_t n_samples, int32_t C, const int32_t* chrom_off)
-{
-  if (sample < 0 || sample >= n_samples) return 4;
-  if (chrom < 0 || chrom >= C) return 2;
-  if (first > last) return 1;
-  if (first < chrom_off[chrom] || last >= chrom_off[chrom + 1]) return 3;
-  return 0;
-}
+using edrows::row_fault;     // a row against the design: the call form (ed_rows.hpp)
 
 // The items of rows (first[r], last[r]), r = 0 .. n_rows - 1.  Returns 0; 1: a row with first > last or first < 0 (nothing is kept);
 // 2: more rows than kMaxRows, or more items than max_items (<= kMaxItems).

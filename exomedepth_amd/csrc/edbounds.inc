@@ -168,12 +168,7 @@ try {
     return ed_fail(ED_ERR_INVALID, "ed_plan_call_bounds: bad arguments");
   double thi, tlo;
   if (!bounds_thresholds(level, thi, tlo)) return ed_fail(ED_ERR_INVALID, "ed_plan_call_bounds: level must lie in (0, 1), got %g", level);
-  for (int64_t r = 0; r < n_calls; ++r) {
-    const ed_call& c = calls[r];
-    if (c.sample < 0 || c.sample >= n_samples || c.chrom < 0 || c.chrom >= p->C || c.start_exon > c.end_exon ||
-        c.start_exon < p->chrom_off[c.chrom] || c.end_exon >= p->chrom_off[c.chrom + 1])
-      return ed_fail(ED_ERR_INVALID, "ed_plan_call_bounds: row %lld does not lie inside its chromosome / the samples", (long long)r);
-  }
+  if (int rc = check_call_rows("ed_plan_call_bounds", p, calls, n_calls, n_samples)) return rc;
   if (n_calls == 0) return ED_OK;
   if (int rc = require_device()) return rc;
   HIP_TRY(hipSetDevice(p->device));
@@ -200,22 +195,16 @@ try {
   if (k <= 0) return ED_OK;
   if (!host_out) return ed_fail(ED_ERR_INVALID, "NULL output");
   if (int rc = ensure_post(b)) return rc;
-  if ((size_t)k * sizeof(ed_call_bounds) > b->d_cbounds.bytes()) {
-    const int64_t want = std::max<int64_t>(k + k / 4, 4096);
-    if (b->d_cbounds.reserve((size_t)want * sizeof(ed_call_bounds)) != hipSuccess)
-      return ed_fail(ED_ERR_NOMEM, "call bounds: cannot allocate %lld records", (long long)want);
-  }
+  if (int rc = grow_records(b->req.d_cbounds, k, "call bounds")) return rc;
+  EventSet<2>& ev = b->req.bounds_ev;
   const bool timed = b->timing;
-  if (timed) {
-    for (auto& e : b->bounds_ev) { if (!e) HIP_TRY(e.create()); }
-    HIP_TRY(hipEventRecord(b->bounds_ev[0], b->stream));
-  }
-  if (int rc = bounds_launch(b->plan, b->d_calls.get(), k, b->d_loglik.get(), b->S, b->post.d_beta.get(), b->post.d_logpost.get(), thi, tlo,
-                             b->d_cbounds.get(), b->stream))
+  if (timed) { HIP_TRY(ev.ready()); HIP_TRY(ev.record(0, b->stream)); }
+  if (int rc = bounds_launch(b->plan, b->d_calls.get(), k, b->d_loglik.get(), b->S, b->req.post.d_beta.get(), b->req.post.d_logpost.get(), thi, tlo,
+                             b->req.d_cbounds.get(), b->stream))
     return rc;
-  if (timed) HIP_TRY(hipEventRecord(b->bounds_ev[1], b->stream));
-  b->bounds_stamp = timed ? b->post_passes : -1;
-  return ed_d2h(host_out, b->d_cbounds, (size_t)k * sizeof(ed_call_bounds), b->stream);
+  if (timed) HIP_TRY(ev.record(1, b->stream));
+  ev.live = timed;
+  return ed_d2h(host_out, b->req.d_cbounds, (size_t)k * sizeof(ed_call_bounds), b->stream);
 }
 ED_CATCH("ed_batch_copy_call_bounds")
 
@@ -224,11 +213,6 @@ ED_CATCH("ed_batch_copy_call_bounds")
 ED_EXPORT int ed_batch_call_bounds_ms(ed_batch* b, float* ms)
 try {
   if (!b || !ms) return ed_fail(ED_ERR_INVALID, "NULL argument");
-  *ms = 0.f;
-  if (!b->post_valid || b->bounds_stamp != b->post_passes) return ED_OK;
-  HIP_TRY(hipSetDevice(b->plan->device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipEventElapsedTime(ms, b->bounds_ev[0], b->bounds_ev[1]));
-  return ED_OK;
+  return request_ms(b, b->req.bounds_ev, 0, 1, ms);
 }
 ED_CATCH("ed_batch_call_bounds_ms")

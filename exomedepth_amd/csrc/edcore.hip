@@ -56,10 +56,12 @@
 #include "ed_mix_plan.hpp"
 #include "ed_power_plan.hpp"
 #include "ed_ratio_plan.hpp"
+#include "ed_rows.hpp"
 
 using edown::DevBuf;
 using edown::PinBuf;
 using edown::Event;
+using edown::EventSet;
 using edown::Stream;
 
 #define ED_EXPORT extern "C" __attribute__((visibility("default")))
@@ -1337,6 +1339,44 @@ struct CtabSet {     // depth-binned model, tabulated constants (edbins.inc)
   bool made() const { return (bool)d_ctab; }
 };
 
+// strides of a count matrix between exons (ce) and between samples (cs): layout 0 is [E][S], layout 1 [S][E]
+struct CountStrides { int64_t ce, cs; };
+static CountStrides count_strides(int layout, int64_t E, int64_t S) { return layout ? CountStrides{1, E} : CountStrides{S, 1}; }
+
+// What a batch's last run was given.  Borrowed: the call decoration and the copy-ratio profile read the caller's arrays again.
+struct RunInputs {
+  const int32_t* test = nullptr, * ref = nullptr;       // count matrices, `cb` bytes per count, in `layout` (counts_layout at the run)
+  const double* phi = nullptr, * expected = nullptr;    // per sample only where `plain`: ed_batch_run, neither depth-binned nor covariate
+  int layout = 0, cb = 4;
+  bool plain = true;
+  const double* cov_X = nullptr, * cov_beta = nullptr;  // covariate model of the run (edcov.inc): expected is per exon
+  int cov_K = -1;
+  bool async = false;        // the run left its tail on `fin` (done_ev marks its end); set by the run's last stage
+};
+
+// What a batch makes from its last run when somebody asks: a run invalidates all of it (run_begins), the first request
+// makes its result behind the run on the batch's stream, a second launches nothing.  Buffers and events are kept from run to run.
+struct OnRequest {
+  bool rows_valid = true;    // d_loglik holds the [E][3][S] form (emit mode 2 makes it from the sample-major matrix: ensure_loglik_rows)
+  bool path_valid = true;    // d_path holds the byte-per-exon path (ensure_path makes it from ppath)
+  bool post_valid = false, score_valid = false;   // `post` / `d_score` hold the run's (ensure_post, edpost.inc; ensure_score, edscore.inc)
+  int64_t post_passes = 0, score_passes = 0;      // times ensure_post / ensure_score have enqueued their passes
+  PostSet post;
+  DevBuf<double> d_score;            // [C][2][S] d logZ / d t, d logZ / d L of every chain
+  DevBuf<ed_call_info> d_info;       // one record per call, grow-only (grow_records): decoration of the call table,
+  DevBuf<ed_call_post> d_cpost;      // ... posterior summary,
+  DevBuf<ed_call_bounds> d_cbounds;  // ... breakpoint intervals (edbounds.inc)
+  // with `timing`, around k_fb_backward / k_fb_forward, k_call_post (read only while post_ev is live), k_fb_score, k_call_bounds and the
+  // last profile request's kernels (edratio.inc).  A set is live while its times belong to the last run's result.
+  EventSet<3> post_ev;
+  EventSet<2> cpost_ev, score_ev, bounds_ev, ratio_ev;
+  void run_begins(bool rows, bool path)
+  {
+    rows_valid = rows; path_valid = path; post_valid = score_valid = false;
+    post_ev.drop(); cpost_ev.drop(); score_ev.drop(); bounds_ev.drop(); ratio_ev.drop();
+  }
+};
+
 // Members are destroyed in reverse order of declaration, and ed_batch_destroy relies on it: the streams are declared first (they go
 // last, after every buffer and event), the fit and bins workspaces last (they go first).  DevBuf / Event / Stream members are owned;
 // raw pointers are borrowed (the plan, the caller's arrays, the cohort's epoch) and say so.
@@ -1377,8 +1417,6 @@ struct ed_batch {
   DevBuf<ed_call> d_calls;       // the call table, grow-only (ed_batch_n_calls regrows it when a run needs more records)
   int64_t calls_cap() const { return (int64_t)(d_calls.bytes() / sizeof(ed_call)); }
   CtabSet ctab;
-  DevBuf<ed_call_info> d_info;   // decoration of the call table, grow-only (hipFree would synchronise the device and with it
-                                 // every other batch of a pipeline)
   int bins_form = 0;                 // form the last ed_batch_fit_bins took (ed_batch_fit_bins_form)
   int64_t bins_unconverged = 0;      // samples the last depth-binned fit left short of its tolerance (ed_batch_fit_bins_n_unconverged)
   int bins_pieces = 1;               // launches the depth-binned emission kernel is cut into (the cohort pipeline sets it)
@@ -1392,7 +1430,7 @@ struct ed_batch {
   // Emission launch cut in two (single-group mode only): the first `split_frac` of the workgroups, an event, the rest.  The
   // cohort pipeline (edcohort.inc) makes the NEXT slab's dispersion fit wait for that event, so that the fit is issued --
   // in stream order, whatever the host's timing -- while this slab's emissions are under way.
-  // borrowed from the caller (device arrays of the cohort pipeline or of the last run; never freed here): src_*, prepared_*, d_mix, last_*
+  // borrowed from the caller (device arrays of the cohort pipeline or of the last run; never freed here): src_*, prepared_*, d_mix, last.*
   const double* src_phi = nullptr;      // cohort pipeline, given parameters: k_sample_consts of the next run / prepare reads (phi, expected) from
   const double* src_exp = nullptr;      // here and writes the copies the run is handed (the slot's arrays); cleared when consumed
   bool prepared_zeroed = false;         // ... batch_prepare also zeroed the run's counters (the cohort says when that is safe)
@@ -1407,38 +1445,12 @@ struct ed_batch {
   bool split_recorded = false;          // the last run recorded split_ev
   bool own_queues = false;              // streams of this batch are created with a (full) CU mask: a hardware queue each
   bool async_tail = false;
-  bool last_run_async = false;          // the last run left its tail on `fin` (done_ev marks its end)
   Event done_ev, fork_ev;
-  int last_layout = 0;                  // counts_layout of the last run's inputs
   int counts_bits = 32;                 // 32: int32 counts; 16: uint16 (sample-major table mode only: ed_batch_set_counts_bits)
-  int last_cb = 4;                      // bytes per count of the last run's inputs
   int cb() const { return counts_bits == 16 ? 2 : 4; }
-  const int32_t* last_test = nullptr;   // inputs of the last ed_batch_run (for ed_batch_copy_call_info)
-  const int32_t* last_ref = nullptr;
-  const double* last_expected = nullptr;
-  const double* last_phi = nullptr;     // ... its dispersions (edratio.inc); per sample only where last_plain
-  bool last_plain = true;               // the last run was ed_batch_run: neither depth-binned nor covariate
-  const double* last_cov_X = nullptr;   // covariate model of the last run (edcov.inc): expected is per exon
-  const double* last_cov_beta = nullptr;
-  int last_cov_K = -1;
   bool ran = false;
-  bool path_valid = true;    // d_path holds the byte-per-exon path of the last run; a run clears it, ensure_path makes the path from ppath
-  bool post_valid = false;   // `post` holds the posterior of the last run; a run clears it, ensure_post runs the two passes (edpost.inc)
-  int64_t post_passes = 0;   // times ensure_post has enqueued them
-  PostSet post;
-  DevBuf<ed_call_post> d_cpost;  // per-call posterior summary, grow-only (as d_info)
-  Event post_ev[5];              // with `timing`: around k_fb_backward / k_fb_forward (0..2) and k_call_post (3, 4); made on first use
-  bool post_timed = false, cpost_timed = false;
-  bool score_valid = false;  // `d_score` holds the transition score of the last run; a run clears it, ensure_score runs the pass (edscore.inc)
-  int64_t score_passes = 0;  // times ensure_score has enqueued it
-  DevBuf<double> d_score;    // [C][2][S] d logZ / d t, d logZ / d L of every chain; made on the first request
-  Event score_ev[2];         // with `timing`: around k_fb_score; made on first use
-  bool score_timed = false;
-  DevBuf<ed_call_bounds> d_cbounds;  // per-call breakpoint intervals (edbounds.inc), grow-only (as d_cpost)
-  Event bounds_ev[2];        // with `timing`: around k_call_bounds; made on first use
-  int64_t bounds_stamp = -1; // post_passes at the last timed k_call_bounds (its events belong to that posterior)
-  Event ratio_ev[2];         // with `timing`: around k_ratio_profile / k_ratio_sum (edratio.inc); made on first use
-  bool ratio_timed = false;  // they hold the last profile request of the last run; a run clears it
+  RunInputs last;            // what the last run was given
+  OnRequest req;             // what has been made from it since, on request
   bool fused = false;        // run emissions + Viterbi as ONE kernel (edfused.inc) instead of two overlapped ones
   bool keep_loglik = true;   // fused mode only: also write the [E][3][S] likelihood matrix (the S4 `likelihood` slot)
   int fit_hist = 1;          // ed_batch_fit: 1 = iterate on count histograms (one pass over the counts), geometry picked from
@@ -1453,14 +1465,13 @@ struct ed_batch {
   TabSet tab;
   unsigned int cold_cap = 0;
   std::vector<int64_t> seg_t;    // emission segments for k_emit_tab's tile shape (as `seg`; host tables of every mode are made by ed_batch_create)
-  // emit mode 2: the documented [E][3][S] form (d_loglik) is made from the sample-major matrix when an accessor asks (rows_valid)
+  // emit mode 2: the documented [E][3][S] form (d_loglik) is made from the sample-major matrix when an accessor asks (req.rows_valid)
   SmSet sm;
   int64_t Epad = 0;
   std::vector<int64_t> seg_sm;   // segments in blocks of 64 exons (first block, first exon, end exon), job order
   std::vector<edplan::Block> blk_sm;   // ... and the blocks themselves (host copy of sm.d_blk_sm; never empty)
   int vit_waves = 1024;          // waves of that grid: the SIMDs of the device (tab_setup_sm)
   int64_t nblk_sm = 0;
-  bool rows_valid = true;
   int fit_mode = 0;          // ed_batch_fit: 0 = maximum likelihood (Newton); 1 = aod::betabin's procedure (Nelder-Mead from the
                              // glm start, optim()'s defaults) on the same histograms -- ed_batch_set_fit_mode
   bool timing = false;
@@ -1939,7 +1950,7 @@ ED_CATCH("ed_batch_set_async_tail")
 ED_EXPORT int ed_batch_wait(ed_batch* b, void* stream_)
 try {
   if (!b) return ed_fail(ED_ERR_INVALID, "NULL batch");
-  if (b->ran && b->last_run_async && b->done_ev) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream_, b->done_ev, 0));
+  if (b->ran && b->last.async && b->done_ev) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream_, b->done_ev, 0));
   return ED_OK;
 }
 ED_CATCH("ed_batch_wait")
@@ -2062,7 +2073,7 @@ static int bins_ctab_setup(ed_batch* b, size_t bytes_left_out)
 // emit mode 2: the [E][3][S] form of the likelihood matrix, made from the sample-major one when somebody asks for it
 static int ensure_loglik_rows(ed_batch* b)
 {
-  if (b->rows_valid) return ED_OK;
+  if (b->req.rows_valid) return ED_OK;
   HIP_TRY(hipSetDevice(b->plan->device));      // (an accessor may be called from a thread whose current device is another one)
   const int64_t E = b->plan->E, S = b->S;
   if (!b->d_loglik) {
@@ -2073,7 +2084,7 @@ static int ensure_loglik_rows(ed_batch* b)
     hipLaunchKernelGGL(k_ll_sm_to_rows, dim3((unsigned)((E + 63) / 64), (unsigned)((S + 63) / 64), 3), dim3(256), 0, b->stream, b->sm.d_loglik_sm, E, b->Epad, S,
                        b->d_loglik);
   HIP_TRY(hipGetLastError());
-  b->rows_valid = true;
+  b->req.rows_valid = true;
   return ED_OK;
 }
 
@@ -2082,16 +2093,16 @@ static int ensure_loglik_rows(ed_batch* b)
 // (which rewrites ppath) waits for it as it does for the tail.
 static int ensure_path(ed_batch* b)
 {
-  if (b->path_valid) return ED_OK;
+  if (b->req.path_valid) return ED_OK;
   HIP_TRY(hipSetDevice(b->plan->device));
   const ed_plan* p = b->plan;
   if (p->C > 0 && p->E > 0 && p->max_words > 0) {
     hipLaunchKernelGGL(k_path_expand, dim3((unsigned)((b->S + 63) / 64), (unsigned)((p->max_words + 3) / 4), (unsigned)p->C), dim3(256),
                        0, b->stream, b->d_ppath, p->d_chrom_off, p->d_tile_off, b->S, b->d_path);
     HIP_TRY(hipGetLastError());
-    if (b->last_run_async && b->done_ev) HIP_TRY(hipEventRecord(b->done_ev, b->stream));
+    if (b->last.async && b->done_ev) HIP_TRY(hipEventRecord(b->done_ev, b->stream));
   }
-  b->path_valid = true;
+  b->req.path_valid = true;
   return ED_OK;
 }
 
@@ -2193,10 +2204,7 @@ static int run_open(Run& r, ed_batch* b, const int32_t* d_test, const int32_t* d
   r.b = b; r.d_test = d_test; r.d_ref = d_ref; r.d_phi = d_phi; r.d_expected = d_expected; r.mixture = mixture; r.em = &em;
   r.tabm = r.plain && b->emit_mode >= 1 && !b->fused;
   r.tabsm = r.tabm && b->emit_mode == 2;
-  b->rows_valid = !r.tabsm;
-  b->path_valid = kEagerPath && !b->fused;   // the byte path is made when it is asked for (ensure_path)
-  b->post_valid = false;                      // ... and so is the posterior (ensure_post)
-  b->score_valid = false;                     // ... and the transition score (ensure_score)
+  b->req.run_begins(!r.tabsm, kEagerPath && !b->fused);   // (the byte path is made when it is asked for, as everything in `req`)
   r.cl1 = b->counts_layout == 1;
   if (r.cl1 && !r.tabsm) return ed_fail(ED_ERR_STATE, "ed_batch_run: sample-major counts (ed_batch_set_counts_layout(batch, 1)) are served by emit mode 2 only");
   if (b->counts_bits == 16 && !(r.cl1 && r.tabsm)) return ed_fail(ED_ERR_STATE, "ed_batch_run: 16-bit counts (ed_batch_set_counts_bits(batch, 16)) are served by counts_layout 1 + emit mode 2 only");
@@ -2207,12 +2215,12 @@ static int run_open(Run& r, ed_batch* b, const int32_t* d_test, const int32_t* d
   r.tail = r.async ? b->fin : r.st;
   if (b->timing) { if (int rc = fold_run_times(b)) return rc; }
   // the previous run's asynchronous tail still reads the buffers -- whatever the mode of THIS run
-  if (b->ran && b->last_run_async && b->done_ev) HIP_TRY(hipStreamWaitEvent(r.st, b->done_ev, 0));
+  if (b->ran && b->last.async && b->done_ev) HIP_TRY(hipStreamWaitEvent(r.st, b->done_ev, 0));
   b->stream = r.tail;
   b->split_recorded = false;
-  b->last_test = d_test; b->last_ref = d_ref; b->last_expected = d_expected; b->last_layout = b->counts_layout; b->last_cb = r.cb;
-  b->last_phi = d_phi; b->last_plain = r.plain; b->ratio_timed = false;
-  b->last_cov_X = em.cov ? em.X : nullptr; b->last_cov_K = em.cov ? em.K : -1; b->last_cov_beta = em.cov ? em.beta : nullptr;
+  RunInputs& in = b->last;
+  in.test = d_test; in.ref = d_ref; in.phi = d_phi; in.expected = d_expected; in.layout = b->counts_layout; in.cb = r.cb; in.plain = r.plain;
+  in.cov_X = em.cov ? em.X : nullptr; in.cov_K = em.cov ? em.K : -1; in.cov_beta = em.cov ? em.beta : nullptr;
   return ED_OK;
 }
 
@@ -2341,10 +2349,11 @@ static int run_group_emissions(const Run& r, size_t g)
   }
   if (r.tabm && nblk > 0) {  // the cells outside their sample's tables and the samples without tables (returns at once when there are none)
     const bool csm = r.cl1 || r.tabsm;       // counts walked sample-major ([S][E]: the caller's, or this mode's transposed copy)
+    const CountStrides cst = count_strides(csm, E, S);
     hipLaunchKernelGGL(k_tab_cold, dim3(1024), dim3(256), 0, r.st, csm ? (r.cl1 ? r.d_test : b->sm.d_test_sm) : r.d_test, csm ? (r.cl1 ? r.d_ref : b->sm.d_ref_sm) : r.d_ref,
                        b->d_consts, b->d_cflags, b->tab.d_tdims, b->tab.d_cold_list, b->tab.d_cold_n,
                        b->cold_cap, b->tab.d_seg_t, j0, j1, S, r.tabsm ? b->sm.d_loglik_sm : b->d_loglik, b->d_nerr, r.tabsm ? (int64_t)1 : 3 * S,
-                       r.tabsm ? b->Epad : S, r.tabsm ? 3 * b->Epad : (int64_t)1, csm ? (int64_t)1 : S, csm ? E : (int64_t)1, b->tab.d_notab, b->d_nerr + 2, r.cl1 ? r.cb : 4);
+                       r.tabsm ? b->Epad : S, r.tabsm ? 3 * b->Epad : (int64_t)1, cst.ce, cst.cs, b->tab.d_notab, b->d_nerr + 2, r.cl1 ? r.cb : 4);
   }
   else if (r.plain && nblk > 0)   // the out-of-domain tasks of this group, if k_emit_batch met any (returns at once otherwise)
     hipLaunchKernelGGL(k_emit_cold, dim3(512), dim3(256), 0, r.st, r.d_test, r.d_ref, b->d_consts, b->d_seg, j0, j1, S, b->d_loglik,
@@ -2442,7 +2451,7 @@ static int run_tail(const Run& r)
   if (r.async) HIP_TRY(hipEventRecord(b->done_ev, r.tail));
   HIP_TRY(hipGetLastError());
   b->ran = true;
-  b->last_run_async = r.async;
+  b->last.async = r.async;
   b->have_run_times = b->timing;
   return ED_OK;
 }
@@ -2546,7 +2555,7 @@ ED_EXPORT int64_t ed_batch_n_samples(const ed_batch* b) { return b ? b->S : 0; }
 ED_EXPORT const double* ed_batch_loglik(const ed_batch* b)
 {
   if (!b || !(b->keep_loglik || !b->fused)) return nullptr;
-  if (!b->rows_valid && ensure_loglik_rows(const_cast<ed_batch*>(b)) != ED_OK) return nullptr;   // (emit mode 2: made on the run's stream)
+  if (!b->req.rows_valid && ensure_loglik_rows(const_cast<ed_batch*>(b)) != ED_OK) return nullptr;   // (emit mode 2: made on the run's stream)
   return b->d_loglik;
 }
 
@@ -2646,7 +2655,7 @@ ED_EXPORT const uint8_t* ed_batch_path(const ed_batch* b_)
 {
   ed_batch* b = const_cast<ed_batch*>(b_);
   if (!b) return nullptr;
-  if (!b->path_valid) {
+  if (!b->req.path_valid) {
     if (ensure_path(b) != ED_OK) return nullptr;
     if (hipStreamSynchronize(b->stream) != hipSuccess) { (void)ed_fail(ED_ERR_HIP, "ed_batch_path: the run or the path's expansion failed"); return nullptr; }
   }
@@ -2660,6 +2669,47 @@ static int batch_ready(ed_batch* b)
   if (!b->ran) return ed_fail(ED_ERR_STATE, "no ed_batch_run has been issued on this batch");
   HIP_TRY(hipSetDevice(b->plan->device));
   HIP_TRY(hipStreamSynchronize(b->stream));
+  return ED_OK;
+}
+
+// ---- shared by the entries that make something on request (edpost.inc, edscore.inc, edbounds.inc, edmix.inc, edpower.inc, edratio.inc) ----
+// a per-call record buffer of at least k records: grow-only, with headroom (hipFree would synchronise the device, and with it every
+// other batch of a pipeline)
+template <class T>
+static int grow_records(DevBuf<T>& buf, int64_t k, const char* what)
+{
+  if ((size_t)k * sizeof(T) <= buf.bytes()) return ED_OK;
+  const int64_t want = std::max<int64_t>(k + k / 4, 4096);
+  if (buf.reserve((size_t)want * sizeof(T)) != hipSuccess) return ed_fail(ED_ERR_NOMEM, "%s: cannot allocate %lld records", what, (long long)want);
+  return ED_OK;
+}
+
+// the time between events i and j of a request's set, 0 unless the set is live; synchronises the batch's stream
+template <int N>
+static int request_ms(ed_batch* b, const EventSet<N>& set, int i, int j, float* ms)
+{
+  *ms = 0.f;
+  if (!set.live) return ED_OK;
+  HIP_TRY(hipSetDevice(b->plan->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(set.elapsed(i, j, ms));
+  return ED_OK;
+}
+
+static int check_counts_args(const char* entry, int layout, int64_t n_samples)
+{
+  if (layout != 0 && layout != 1) return ed_fail(ED_ERR_INVALID, "%s: layout %d is neither 0 ([E][S]) nor 1 ([S][E])", entry, layout);
+  if (n_samples < 1 || n_samples > (1 << 20)) return ed_fail(ED_ERR_INVALID, "%s: n_samples is outside 1 .. 1048576", entry);
+  return ED_OK;
+}
+
+static int check_call_rows(const char* entry, const ed_plan* p, const ed_call* rows, int64_t n_rows, int64_t n_samples)
+{
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const ed_call& c = rows[r];
+    if (edrows::row_fault(c.sample, c.chrom, c.start_exon, c.end_exon, n_samples, p->C, p->chrom_off.data()))
+      return ed_fail(ED_ERR_INVALID, "%s: row %lld does not lie inside its chromosome / the samples", entry, (long long)r);
+  }
   return ED_OK;
 }
 
@@ -2718,18 +2768,15 @@ try {
   const int64_t k = std::min(n, cap);
   if (k <= 0) return ED_OK;
   if (!host_info) return ed_fail(ED_ERR_INVALID, "NULL output");
-  if ((size_t)k * sizeof(ed_call_info) > b->d_info.bytes()) {
-    const int64_t cap = std::max<int64_t>(k + k / 4, 4096);
-    if (b->d_info.reserve((size_t)cap * sizeof(ed_call_info)) != hipSuccess)
-      return ed_fail(ED_ERR_NOMEM, "call decoration: cannot allocate %lld records", (long long)cap);
-  }
+  if (int rc = grow_records(b->req.d_info, k, "call decoration")) return rc;
+  const RunInputs& in = b->last;
+  const CountStrides cst = count_strides(in.layout, b->plan->E, b->S);
   hipLaunchKernelGGL(k_call_info, dim3((unsigned)((k + 127) / 128)), dim3(128), 0, b->stream, b->d_calls, k,
-                     (b->keep_loglik || !b->fused) ? (b->rows_valid ? b->d_loglik : b->sm.d_loglik_sm) : (double*)nullptr, b->d_consts, b->last_test, b->last_ref,
-                     b->last_expected, b->S, b->d_info, b->last_cov_X, b->last_cov_K, b->last_cov_beta, b->rows_valid ? 3 * b->S : (int64_t)1,
-                     b->rows_valid ? b->S : b->Epad, b->rows_valid ? (int64_t)1 : 3 * b->Epad, b->last_layout ? (int64_t)1 : b->S,
-                     b->last_layout ? b->plan->E : (int64_t)1, b->last_cb);
+                     (b->keep_loglik || !b->fused) ? (b->req.rows_valid ? b->d_loglik : b->sm.d_loglik_sm) : (double*)nullptr, b->d_consts, in.test, in.ref,
+                     in.expected, b->S, b->req.d_info, in.cov_X, in.cov_K, in.cov_beta, b->req.rows_valid ? 3 * b->S : (int64_t)1,
+                     b->req.rows_valid ? b->S : b->Epad, b->req.rows_valid ? (int64_t)1 : 3 * b->Epad, cst.ce, cst.cs, in.cb);
   HIP_TRY(hipGetLastError());
-  if (int rc = ed_d2h(host_info, b->d_info, (size_t)k * sizeof(ed_call_info), b->stream)) return rc;
+  if (int rc = ed_d2h(host_info, b->req.d_info, (size_t)k * sizeof(ed_call_info), b->stream)) return rc;
   return ED_OK;
 }
 ED_CATCH("ed_batch_copy_call_info")
@@ -2775,9 +2822,10 @@ try {
   HIP_TRY(hipMemsetAsync(dcnt.get(), 0, 24, b->stream));
   const int64_t rows_per_block = (int64_t)(kEmitBlock / 64) * kVerifyRun;
   const int64_t eblk = (E + rows_per_block - 1) / rows_per_block;
+  const CountStrides cst = count_strides(b->counts_layout, E, S);
   hipLaunchKernelGGL(k_emit_verify, dim3((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(eblk, 65535), (unsigned)((eblk + 65534) / 65535)),
                      dim3(kEmitBlock), 0, b->stream, d_test, d_ref, d_phi, d_expected, mixture, E, S, b->d_loglik,
-                     dcnt.as<unsigned long long>(), dfirst.as<ed_emit_mismatch>(), cap, b->counts_layout ? (int64_t)1 : S, b->counts_layout ? E : (int64_t)1, b->d_mix);
+                     dcnt.as<unsigned long long>(), dfirst.as<ed_emit_mismatch>(), cap, cst.ce, cst.cs, b->d_mix);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   unsigned long long c[3] = {0, 0, 0};
@@ -2810,9 +2858,10 @@ try {
   HIP_TRY(hipMemsetAsync(dcnt.get(), 0, 40, b->stream));
   const int64_t rows_per_block = (int64_t)(kEmitBlock / 64) * kVerifyRun;
   const int64_t eblk = (E + rows_per_block - 1) / rows_per_block;
+  const CountStrides cst = count_strides(b->counts_layout, E, S);
   hipLaunchKernelGGL(k_emit_verify_tol, dim3((unsigned)((S + 63) / 64), (unsigned)std::min<int64_t>(eblk, 65535), (unsigned)((eblk + 65534) / 65535)),
                      dim3(kEmitBlock), 0, b->stream, d_test, d_ref, d_phi, d_expected, mixture, E, S, b->d_loglik, rel_tol, abs_tol,
-                     dcnt.as<unsigned long long>(), dfirst.as<ed_emit_mismatch>(), cap, b->counts_layout ? (int64_t)1 : S, b->counts_layout ? E : (int64_t)1, b->counts_layout ? b->cb() : 4,
+                     dcnt.as<unsigned long long>(), dfirst.as<ed_emit_mismatch>(), cap, cst.ce, cst.cs, b->counts_layout ? b->cb() : 4,
                      b->d_mix);
   HIP_TRY(hipGetLastError());
   unsigned long long c[5] = {0, 0, 0, 0, 0};

@@ -157,8 +157,7 @@ try {
   if (!p) return ed_fail(ED_ERR_INVALID, "ed_plan_mixture_profile: NULL plan");
   if (n_grid < 1 || n_grid > edmix::kMaxGrid)
     return ed_fail(ED_ERR_INVALID, "ed_plan_mixture_profile: n_grid = %d is outside 1 .. %d", n_grid, edmix::kMaxGrid);
-  if (layout != 0 && layout != 1) return ed_fail(ED_ERR_INVALID, "ed_plan_mixture_profile: layout %d is neither 0 ([E][S]) nor 1 ([S][E])", layout);
-  if (n_samples < 1 || n_samples > (1 << 20)) return ed_fail(ED_ERR_INVALID, "ed_plan_mixture_profile: n_samples is outside 1 .. 1048576");
+  if (int rc = check_counts_args("ed_plan_mixture_profile", layout, n_samples)) return rc;
   if (!d_test || !d_ref || !d_phi || !d_expected || !d_grid || !d_logev) return ed_fail(ED_ERR_INVALID, "ed_plan_mixture_profile: NULL array");
   if (p->C > 65535) return ed_fail(ED_ERR_INVALID, "ed_plan_mixture_profile: more than 65535 chromosomes");
   if (int rc = require_device()) return rc;
@@ -169,8 +168,9 @@ try {
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(d_logev, 0, (size_t)n_grid * p->C * S * 8, st));       // an empty chromosome is in no job: its log-evidence is 0
   if (p->n_mix_jobs <= 0) return ED_OK;
+  const CountStrides cst = count_strides(layout, p->E, S);
   hipLaunchKernelGGL(k_mix_profile, dim3((unsigned)S, (unsigned)p->n_mix_jobs), dim3(edmix::kThreads), 0, st, d_test, d_ref,
-                     layout ? (int64_t)1 : S, layout ? p->E : (int64_t)1, d_phi, d_expected, d_grid, n_grid, (const double*)p->d_lt3.get(),
+                     cst.ce, cst.cs, d_phi, d_expected, d_grid, n_grid, (const double*)p->d_lt3.get(),
                      p->c0, p->c1, (const int32_t*)p->d_chrom_off.get(), (const int32_t*)p->d_mix_jobs.get(), p->C, S, d_logev);
   HIP_TRY(hipGetLastError());
   return ED_OK;

@@ -293,12 +293,7 @@ ED_EXPORT int ed_plan_call_posterior(const ed_plan* p, const ed_call* calls, int
 try {
   if (!p || n_calls < 0 || n_samples <= 0 || (n_calls > 0 && (!calls || !out || !d_loglik || !d_work || !d_logpost || !d_log_evidence)))
     return ed_fail(ED_ERR_INVALID, "ed_plan_call_posterior: bad arguments");
-  for (int64_t r = 0; r < n_calls; ++r) {
-    const ed_call& c = calls[r];
-    if (c.sample < 0 || c.sample >= n_samples || c.chrom < 0 || c.chrom >= p->C || c.start_exon > c.end_exon ||
-        c.start_exon < p->chrom_off[c.chrom] || c.end_exon >= p->chrom_off[c.chrom + 1])
-      return ed_fail(ED_ERR_INVALID, "ed_plan_call_posterior: row %lld does not lie inside its chromosome / the samples", (long long)r);
-  }
+  if (int rc = check_call_rows("ed_plan_call_posterior", p, calls, n_calls, n_samples)) return rc;
   if (n_calls == 0) return ED_OK;
   if (int rc = require_device()) return rc;
   HIP_TRY(hipSetDevice(p->device));
@@ -320,7 +315,7 @@ ED_CATCH("ed_plan_call_posterior")
 // (which rewrites the likelihood matrix) waits for them as it does for the tail.  The buffers are there or they are not.
 static int ensure_post(ed_batch* b)
 {
-  if (b->post_valid) return ED_OK;
+  if (b->req.post_valid) return ED_OK;
   if (b->fused && !b->keep_loglik)
     return ed_fail(ED_ERR_STATE, "the posterior reads the likelihood matrix, which this fused batch does not keep (ed_batch_keep_loglik(batch, 1))");
   HIP_TRY(hipSetDevice(b->plan->device));
@@ -328,28 +323,26 @@ static int ensure_post(ed_batch* b)
   if (!b->d_loglik) return ed_fail(ED_ERR_STATE, "the posterior reads the likelihood matrix, which is not kept (ed_batch_keep_loglik)");
   const ed_plan* p = b->plan;
   const int64_t E = p->E, S = b->S, C = p->C;
-  if (!b->post.made()) {
+  if (!b->req.post.made()) {
     PostSet t;
     if (t.d_beta.alloc((size_t)std::max<int64_t>(E, 1) * 3 * S * 8) != hipSuccess ||
         t.d_logpost.alloc((size_t)std::max<int64_t>(E, 1) * 2 * S * 8) != hipSuccess ||
         t.d_logev.alloc((size_t)std::max<int64_t>(C, 1) * S * 8) != hipSuccess)
       return ed_fail(ED_ERR_NOMEM, "posterior: cannot allocate 40 bytes per cell (E=%lld S=%lld)", (long long)E, (long long)S);
-    b->post = std::move(t);
+    b->req.post = std::move(t);
   }
   const bool timed = b->timing && p->C > 0 && b->n_jobs > 0;
-  if (timed) {
-    for (auto& e : b->post_ev) { if (!e) HIP_TRY(e.create()); }
-    HIP_TRY(hipEventRecord(b->post_ev[0], b->stream));
-  }
-  if (int rc = post_launch(p, b->d_loglik, 3 * S, S, 1, S, b->post.d_beta, b->post.d_logpost, b->post.d_logev, b->d_job_off, b->d_job_chrom,
-                           b->n_jobs, b->stream, timed ? b->post_ev[1].get() : nullptr))
+  EventSet<3>& ev = b->req.post_ev;
+  ev.drop(); b->req.cpost_ev.drop(); b->req.bounds_ev.drop();     // they time readers of the posterior that these passes replace
+  if (timed) { HIP_TRY(ev.ready()); HIP_TRY(ev.record(0, b->stream)); }
+  if (int rc = post_launch(p, b->d_loglik, 3 * S, S, 1, S, b->req.post.d_beta, b->req.post.d_logpost, b->req.post.d_logev, b->d_job_off, b->d_job_chrom,
+                           b->n_jobs, b->stream, timed ? ev.ev[1].get() : nullptr))
     return rc;
-  if (timed) HIP_TRY(hipEventRecord(b->post_ev[2], b->stream));
-  b->post_timed = timed;
-  b->cpost_timed = false;
-  if (b->last_run_async && b->done_ev) HIP_TRY(hipEventRecord(b->done_ev, b->stream));
-  ++b->post_passes;
-  b->post_valid = true;
+  if (timed) HIP_TRY(ev.record(2, b->stream));
+  ev.live = timed;
+  if (b->last.async && b->done_ev) HIP_TRY(hipEventRecord(b->done_ev, b->stream));
+  ++b->req.post_passes;
+  b->req.post_valid = true;
   return ED_OK;
 }
 
@@ -358,7 +351,7 @@ try {
   if (int rc = batch_ready(b)) return rc;
   if (!host_logpost) return ed_fail(ED_ERR_INVALID, "NULL output");
   if (int rc = ensure_post(b)) return rc;
-  return ed_d2h(host_logpost, b->post.d_logpost, (size_t)b->plan->E * 2 * b->S * 8, b->stream);
+  return ed_d2h(host_logpost, b->req.post.d_logpost, (size_t)b->plan->E * 2 * b->S * 8, b->stream);
 }
 ED_CATCH("ed_batch_copy_posterior")
 
@@ -367,7 +360,7 @@ try {
   if (int rc = batch_ready(b)) return rc;
   if (!host_log_evidence) return ed_fail(ED_ERR_INVALID, "NULL output");
   if (int rc = ensure_post(b)) return rc;
-  return ed_d2h(host_log_evidence, b->post.d_logev, (size_t)b->plan->C * b->S * 8, b->stream);
+  return ed_d2h(host_log_evidence, b->req.post.d_logev, (size_t)b->plan->C * b->S * 8, b->stream);
 }
 ED_CATCH("ed_batch_copy_log_evidence")
 
@@ -376,11 +369,11 @@ ED_EXPORT const double* ed_batch_posterior(const ed_batch* b_)
 {
   ed_batch* b = const_cast<ed_batch*>(b_);
   if (!b || !b->ran) { (void)ed_fail(ED_ERR_STATE, "ed_batch_posterior: no ed_batch_run has been issued on this batch"); return nullptr; }
-  if (!b->post_valid) {
+  if (!b->req.post_valid) {
     if (ensure_post(b) != ED_OK) return nullptr;
     if (hipStreamSynchronize(b->stream) != hipSuccess) { (void)ed_fail(ED_ERR_HIP, "ed_batch_posterior: the run or the posterior passes failed"); return nullptr; }
   }
-  return b->post.d_logpost;
+  return b->req.post.d_logpost;
 }
 
 ED_EXPORT int ed_batch_copy_call_posterior(ed_batch* b, ed_call_post* host_post, int64_t cap)
@@ -391,37 +384,30 @@ try {
   if (k <= 0) return ED_OK;
   if (!host_post) return ed_fail(ED_ERR_INVALID, "NULL output");
   if (int rc = ensure_post(b)) return rc;
-  if ((size_t)k * sizeof(ed_call_post) > b->d_cpost.bytes()) {
-    const int64_t want = std::max<int64_t>(k + k / 4, 4096);
-    if (b->d_cpost.reserve((size_t)want * sizeof(ed_call_post)) != hipSuccess)
-      return ed_fail(ED_ERR_NOMEM, "call posterior: cannot allocate %lld records", (long long)want);
-  }
-  const bool timed = b->timing && b->post_timed;
-  if (timed) HIP_TRY(hipEventRecord(b->post_ev[3], b->stream));
+  if (int rc = grow_records(b->req.d_cpost, k, "call posterior")) return rc;
+  EventSet<2>& ev = b->req.cpost_ev;
+  const bool timed = b->timing && b->req.post_ev.live;
+  if (timed) { HIP_TRY(ev.ready()); HIP_TRY(ev.record(0, b->stream)); }
   hipLaunchKernelGGL(k_call_post, dim3((unsigned)((k + 127) / 128)), dim3(128), 0, b->stream, (const ed_call*)b->d_calls.get(), k,
-                     (const double*)b->d_loglik.get(), 3 * b->S, b->S, (int64_t)1, b->plan->d_lt3.get(), b->S, (const double*)b->post.d_beta.get(),
-                     (const double*)b->post.d_logpost.get(), (const double*)b->post.d_logev.get(), b->d_cpost.get());
+                     (const double*)b->d_loglik.get(), 3 * b->S, b->S, (int64_t)1, b->plan->d_lt3.get(), b->S, (const double*)b->req.post.d_beta.get(),
+                     (const double*)b->req.post.d_logpost.get(), (const double*)b->req.post.d_logev.get(), b->req.d_cpost.get());
   HIP_TRY(hipGetLastError());
-  if (timed) { HIP_TRY(hipEventRecord(b->post_ev[4], b->stream)); b->cpost_timed = true; }
-  return ed_d2h(host_post, b->d_cpost, (size_t)k * sizeof(ed_call_post), b->stream);
+  if (timed) { HIP_TRY(ev.record(1, b->stream)); ev.live = true; }
+  return ed_d2h(host_post, b->req.d_cpost, (size_t)k * sizeof(ed_call_post), b->stream);
 }
 ED_CATCH("ed_batch_copy_call_posterior")
 
 // how many times the posterior passes have been enqueued on this batch since it was created (a request after the first launches nothing)
-ED_EXPORT int64_t ed_batch_n_posterior_passes(const ed_batch* b) { return b ? b->post_passes : 0; }
+ED_EXPORT int64_t ed_batch_n_posterior_passes(const ed_batch* b) { return b ? b->req.post_passes : 0; }
 
 // with ed_batch_enable_timing: the times of k_fb_backward, k_fb_forward and (if ed_batch_copy_call_posterior has been called since) k_call_post
 // of the last run's posterior request, from events on its stream; 0 for what was not timed.  Synchronises that stream.
 ED_EXPORT int ed_batch_posterior_ms(ed_batch* b, float ms[3])
 try {
   if (!b || !ms) return ed_fail(ED_ERR_INVALID, "NULL argument");
-  ms[0] = ms[1] = ms[2] = 0.f;
-  if (!b->post_valid || !b->post_timed) return ED_OK;
-  HIP_TRY(hipSetDevice(b->plan->device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipEventElapsedTime(&ms[0], b->post_ev[0], b->post_ev[1]));
-  HIP_TRY(hipEventElapsedTime(&ms[1], b->post_ev[1], b->post_ev[2]));
-  if (b->cpost_timed) HIP_TRY(hipEventElapsedTime(&ms[2], b->post_ev[3], b->post_ev[4]));
-  return ED_OK;
+  ms[2] = 0.f;
+  if (int rc = request_ms(b, b->req.post_ev, 0, 1, &ms[0])) return rc;
+  if (int rc = request_ms(b, b->req.post_ev, 1, 2, &ms[1])) return rc;
+  return b->req.post_ev.live ? request_ms(b, b->req.cpost_ev, 0, 1, &ms[2]) : ED_OK;
 }
 ED_CATCH("ed_batch_posterior_ms")

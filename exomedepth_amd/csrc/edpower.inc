@@ -381,8 +381,7 @@ try {
   if (!out) return ed_fail(ED_ERR_INVALID, "ed_plan_power_map: NULL output");
   *out = nullptr;
   if (!p) return ed_fail(ED_ERR_INVALID, "ed_plan_power_map: NULL plan");
-  if (layout != 0 && layout != 1) return ed_fail(ED_ERR_INVALID, "ed_plan_power_map: layout %d is neither 0 ([E][S]) nor 1 ([S][E])", layout);
-  if (n_samples < 1 || n_samples > (1 << 20)) return ed_fail(ED_ERR_INVALID, "ed_plan_power_map: n_samples is outside 1 .. 1048576");
+  if (int rc = check_counts_args("ed_plan_power_map", layout, n_samples)) return rc;
   if (!phi || !expected || (p->E > 0 && (!test || !ref))) return ed_fail(ED_ERR_INVALID, "ed_plan_power_map: NULL array");
   if (int rc = require_device()) return rc;
   HIP_TRY(hipSetDevice(p->device));
@@ -502,7 +501,7 @@ try {
   if (n_rows > 0 && (!rows || !sums || !n_empty || !price || !n_exons)) return ed_fail(ED_ERR_INVALID, "ed_power_regions: NULL array");
   const ed_plan* p = pm->plan;
   for (int64_t r = 0; r < n_rows; ++r) {
-    const int f = edpower::row_fault(rows[r].chrom, rows[r].start_exon, rows[r].end_exon, p->C, p->chrom_off.data());
+    const int f = edrows::row_fault(rows[r].chrom, rows[r].start_exon, rows[r].end_exon, p->C, p->chrom_off.data());
     if (f == 1) return ed_fail(ED_ERR_INVALID, "ed_power_regions: row %lld has first > last", (long long)r);
     if (f == 2) return ed_fail(ED_ERR_INVALID, "ed_power_regions: row %lld names a chromosome outside the plan", (long long)r);
     if (f == 3)

@@ -186,20 +186,15 @@ static int plan_ratio_profile(const ed_plan* p, const ed_call* rows, int64_t n_r
 {
   if (!edratio::grid_ok(G)) return ed_fail(ED_ERR_INVALID, "ed_plan_ratio_profile: G = %d is outside 1 .. %d", G, edratio::kMaxGrid);
   if (!p) return ed_fail(ED_ERR_INVALID, "ed_plan_ratio_profile: NULL plan");
-  if (layout != 0 && layout != 1) return ed_fail(ED_ERR_INVALID, "ed_plan_ratio_profile: layout %d is neither 0 ([E][S]) nor 1 ([S][E])", layout);
-  if (n_samples < 1 || n_samples > (1 << 20)) return ed_fail(ED_ERR_INVALID, "ed_plan_ratio_profile: n_samples is outside 1 .. 1048576");
+  if (int rc = check_counts_args("ed_plan_ratio_profile", layout, n_samples)) return rc;
   if (n_rows < 0 || n_rows > edratio::kMaxRows) return ed_fail(ED_ERR_INVALID, "ed_plan_ratio_profile: n_rows is outside 0 .. 2^31 - 1");
   if (n_rows > 0 && (!rows || !d_test || !d_ref || !d_phi || !d_expected || !grid || !out)) return ed_fail(ED_ERR_INVALID, "ed_plan_ratio_profile: NULL array");
-  for (int64_t r = 0; r < n_rows; ++r) {
-    const ed_call& c = rows[r];
-    if (edratio::row_fault(c.sample, c.chrom, c.start_exon, c.end_exon, n_samples, p->C, p->chrom_off.data()))
-      return ed_fail(ED_ERR_INVALID, "ed_plan_ratio_profile: row %lld does not lie inside its chromosome / the samples", (long long)r);
-  }
+  if (int rc = check_call_rows("ed_plan_ratio_profile", p, rows, n_rows, n_samples)) return rc;
   if (n_rows == 0) return ED_OK;
   if (int rc = require_device()) return rc;
   HIP_TRY(hipSetDevice(p->device));
-  return ratio_run(rows, n_rows, nullptr, d_test, d_ref, layout ? (int64_t)1 : n_samples, layout ? p->E : (int64_t)1, 4, d_phi, d_expected, grid, G,
-                   out, tail, (hipStream_t)stream, nullptr);
+  const CountStrides cst = count_strides(layout, p->E, n_samples);
+  return ratio_run(rows, n_rows, nullptr, d_test, d_ref, cst.ce, cst.cs, 4, d_phi, d_expected, grid, G, out, tail, (hipStream_t)stream, nullptr);
 }
 
 ED_EXPORT int ed_plan_ratio_profile(const ed_plan* p, const ed_call* rows, int64_t n_rows, const int32_t* d_test, const int32_t* d_ref, int layout,
@@ -226,25 +221,27 @@ ED_CATCH("ed_plan_ratio_profile_dd")
 static int batch_call_ratio_profile(ed_batch* b, const double* grid, int G, double* host_out, double* host_tail, bool want_tail, int64_t cap)
 {
   if (!edratio::grid_ok(G)) return ed_fail(ED_ERR_INVALID, "ed_batch_copy_call_ratio_profile: G = %d is outside 1 .. %d", G, edratio::kMaxGrid);
-  if (b && b->ran && !b->last_plain)
+  if (b && b->ran && !b->last.plain)
     return ed_fail(ED_ERR_STATE, "ed_batch_copy_call_ratio_profile: the last run was a depth-binned or covariate run, which has no single "
                                  "(phi, expected) per sample; the profile is defined for ed_batch_run only");
   int64_t n = 0;
   if (int rc = ed_batch_n_calls(b, &n)) return rc;   // (grows the table if the run needed more records)
   if (cap < n) return ed_fail(ED_ERR_INVALID, "ed_batch_copy_call_ratio_profile: cap = %lld is below the %lld calls of the run (the grid and the output are [G][calls])",
                               (long long)cap, (long long)n);
-  b->ratio_timed = false;
+  EventSet<2>& ev = b->req.ratio_ev;
+  ev.drop();
   if (n <= 0) return ED_OK;
   if (!grid || !host_out || (want_tail && !host_tail)) return ed_fail(ED_ERR_INVALID, "ed_batch_copy_call_ratio_profile: NULL array");
   std::vector<ed_call> rows((size_t)n);
   if (int rc = ed_d2h(rows.data(), b->d_calls, (size_t)n * sizeof(ed_call), b->stream)) return rc;
   const bool timed = b->timing;
-  if (timed) { for (auto& e : b->ratio_ev) { if (!e) HIP_TRY(e.create()); } }
-  if (int rc = ratio_run(rows.data(), n, b->d_calls.get(), b->last_test, b->last_ref, b->last_layout ? (int64_t)1 : b->S,
-                         b->last_layout ? b->plan->E : (int64_t)1, b->last_cb, b->last_phi, b->last_expected, grid, G, host_out, host_tail, b->stream,
-                         timed ? b->ratio_ev : nullptr))
+  if (timed) HIP_TRY(ev.ready());
+  const RunInputs& in = b->last;
+  const CountStrides cst = count_strides(in.layout, b->plan->E, b->S);
+  if (int rc = ratio_run(rows.data(), n, b->d_calls.get(), in.test, in.ref, cst.ce, cst.cs, in.cb, in.phi, in.expected, grid, G, host_out, host_tail,
+                         b->stream, timed ? ev.ev : nullptr))
     return rc;
-  b->ratio_timed = timed;
+  ev.live = timed;
   return ED_OK;
 }
 
@@ -265,12 +262,7 @@ ED_CATCH("ed_batch_copy_call_ratio_profile_dd")
 ED_EXPORT int ed_batch_call_ratio_ms(ed_batch* b, float* ms)
 try {
   if (!b || !ms) return ed_fail(ED_ERR_INVALID, "NULL argument");
-  *ms = 0.f;
-  if (!b->ratio_timed) return ED_OK;
-  HIP_TRY(hipSetDevice(b->plan->device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipEventElapsedTime(ms, b->ratio_ev[0], b->ratio_ev[1]));
-  return ED_OK;
+  return request_ms(b, b->req.ratio_ev, 0, 1, ms);
 }
 ED_CATCH("ed_batch_call_ratio_ms")
 

@@ -207,27 +207,25 @@ ED_CATCH("ed_plan_transition_score")
 // reading their beta and logZ; with an asynchronous tail done_ev is moved behind the score pass as well.
 static int ensure_score(ed_batch* b)
 {
-  if (b->score_valid) return ED_OK;
+  if (b->req.score_valid) return ED_OK;
   if (int rc = ensure_post(b)) return rc;
   const ed_plan* p = b->plan;
   if (int rc = ensure_score_table(p)) return rc;
-  if (!b->d_score) {
-    if (b->d_score.alloc((size_t)std::max<int64_t>(p->C, 1) * 2 * b->S * 8) != hipSuccess)
+  if (!b->req.d_score) {
+    if (b->req.d_score.alloc((size_t)std::max<int64_t>(p->C, 1) * 2 * b->S * 8) != hipSuccess)
       return ed_fail(ED_ERR_NOMEM, "transition score: cannot allocate %lld x 2 x %lld values", (long long)p->C, (long long)b->S);
   }
   const bool timed = b->timing && p->C > 0 && b->n_jobs > 0;
-  if (timed) {
-    for (auto& e : b->score_ev) { if (!e) HIP_TRY(e.create()); }
-    HIP_TRY(hipEventRecord(b->score_ev[0], b->stream));
-  }
-  if (int rc = score_launch(p, b->d_loglik, b->S, b->post.d_beta, b->post.d_logev, b->d_score, b->d_job_off, b->d_job_chrom, b->n_jobs,
+  EventSet<2>& ev = b->req.score_ev;
+  if (timed) { HIP_TRY(ev.ready()); HIP_TRY(ev.record(0, b->stream)); }
+  if (int rc = score_launch(p, b->d_loglik, b->S, b->req.post.d_beta, b->req.post.d_logev, b->req.d_score, b->d_job_off, b->d_job_chrom, b->n_jobs,
                             b->stream))
     return rc;
-  if (timed) HIP_TRY(hipEventRecord(b->score_ev[1], b->stream));
-  b->score_timed = timed;
-  if (b->last_run_async && b->done_ev) HIP_TRY(hipEventRecord(b->done_ev, b->stream));
-  ++b->score_passes;
-  b->score_valid = true;
+  if (timed) HIP_TRY(ev.record(1, b->stream));
+  ev.live = timed;
+  if (b->last.async && b->done_ev) HIP_TRY(hipEventRecord(b->done_ev, b->stream));
+  ++b->req.score_passes;
+  b->req.score_valid = true;
   return ED_OK;
 }
 
@@ -236,12 +234,12 @@ try {
   if (int rc = batch_ready(b)) return rc;
   if (!host_score) return ed_fail(ED_ERR_INVALID, "NULL output");
   if (int rc = ensure_score(b)) return rc;
-  return ed_d2h(host_score, b->d_score, (size_t)b->plan->C * 2 * b->S * 8, b->stream);
+  return ed_d2h(host_score, b->req.d_score, (size_t)b->plan->C * 2 * b->S * 8, b->stream);
 }
 ED_CATCH("ed_batch_copy_transition_score")
 
 // how many times the score pass has been enqueued on this batch since it was created (a request after the first launches nothing)
-ED_EXPORT int64_t ed_batch_n_score_passes(const ed_batch* b) { return b ? b->score_passes : 0; }
+ED_EXPORT int64_t ed_batch_n_score_passes(const ed_batch* b) { return b ? b->req.score_passes : 0; }
 
 // how many times this plan has built and uploaded its table of derivatives (0 before the first request, 1 ever after)
 ED_EXPORT int64_t ed_plan_n_score_tables(const ed_plan* p) { return p ? p->score_tables : 0; }
@@ -251,11 +249,6 @@ ED_EXPORT int64_t ed_plan_n_score_tables(const ed_plan* p) { return p ? p->score
 ED_EXPORT int ed_batch_transition_score_ms(ed_batch* b, float* ms)
 try {
   if (!b || !ms) return ed_fail(ED_ERR_INVALID, "NULL argument");
-  *ms = 0.f;
-  if (!b->score_valid || !b->score_timed) return ED_OK;
-  HIP_TRY(hipSetDevice(b->plan->device));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipEventElapsedTime(ms, b->score_ev[0], b->score_ev[1]));
-  return ED_OK;
+  return request_ms(b, b->req.score_ev, 0, 1, ms);
 }
 ED_CATCH("ed_batch_transition_score_ms")

@@ -93,6 +93,21 @@ int main()
     CHECK(!e && f.get() == raw);
     Event g(std::move(f));
     CHECK(!f && g.get() == raw);
+    EventSet<3> set;                                      // made on first use, kept from then on; live is the user's to set, drop() clears it
+    CHECK(!set.live && !set.ev[0] && !set.ev[2]);
+    const bool have_set = set.ready() == hipSuccess;
+    if (!have_set) (void)hipGetLastError();
+    CHECK(have_set == have_ev && (bool)set.ev[0] == have_set && (bool)set.ev[2] == have_set && !set.live);
+    const hipEvent_t first = set.ev[0].get();
+    CHECK((set.ready() == hipSuccess) == have_set && set.ev[0].get() == first);      // a second call makes nothing new
+    if (have_set) {
+      float ms = -1.f;
+      CHECK(set.record(0, nullptr) == hipSuccess && set.record(2, nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess);
+      CHECK(set.elapsed(0, 2, &ms) == hipSuccess && ms >= 0.f);
+    }
+    set.live = true;
+    set.drop();
+    CHECK(!set.live && set.ev[0].get() == first);         // the events stay
     Stream s, t;
     s.reset();
     CHECK(!s && s.get() == nullptr);
