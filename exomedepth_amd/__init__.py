@@ -11,6 +11,7 @@ from .api import (Batch, Cohort, MultiDevice, DeviceArray, device_count, PinnedA
                   ReadCounter, getBamCounts, count_everted_reads, bed_targets, readcount_geometry,
                   CALL_BOUNDS_DTYPE,
                   PowerMap, detection_power, region_runs, power_geometry, power_from_moments, POWER_DTYPE,
+                  QuantileMap, normal_range, qbetabinom, qbetabinom_ab, quantile_geometry,
                   call_copy_number, copy_number_from_profile, ratio_geometry, CALL_DTYPE, COPY_RATIO_GRID)
 
 __all__ = ["Batch", "Cohort", "MultiDevice", "DeviceArray", "device_count", "PinnedArray", "ExomeDepth", "Plan", "Posterior", "fit_transitions", "fit_prop_tumor", "mixture_geometry", "EdError", "chromosome_order", "cohort_select_reference_sets", "refcohort_last_path", "fit_betabin", "fit_betabin_bins",
@@ -20,4 +21,5 @@ __all__ = ["Batch", "Cohort", "MultiDevice", "DeviceArray", "device_count", "Pin
            "ReadCounter", "getBamCounts", "count_everted_reads", "bed_targets", "readcount_geometry",
            "CALL_BOUNDS_DTYPE",
            "PowerMap", "detection_power", "region_runs", "power_geometry", "power_from_moments", "POWER_DTYPE",
+           "QuantileMap", "normal_range", "qbetabinom", "qbetabinom_ab", "quantile_geometry",
            "call_copy_number", "copy_number_from_profile", "ratio_geometry", "CALL_DTYPE", "COPY_RATIO_GRID"]

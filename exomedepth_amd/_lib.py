@@ -206,6 +206,14 @@ SYMBOLS = [
     ("ed_power_copy_table", C.c_int, [_vp, _i64, _vp, _vp, _i64, C.POINTER(_i64)]),
     ("ed_power_stats", C.c_int, [_vp, _vp, _vp]),
     ("ed_power_geometry", C.c_int, [C.POINTER(_i32)]),
+    ("ed_plan_quantile_map", C.c_int, [C.POINTER(_vp), _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _i64, _vp]),
+    ("ed_quant_free", None, [_vp]),
+    ("ed_quant_regions", C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    ("ed_quant_copy_exons", C.c_int, [_vp, _vp, _vp]),
+    ("ed_quant_copy_table", C.c_int, [_vp, _i64, _vp, _vp, _i64, C.POINTER(_i64)]),
+    ("ed_quant_stats", C.c_int, [_vp, _vp, _vp]),
+    ("ed_quant_geometry", C.c_int, [C.POINTER(_i32)]),
+    ("ed_qbetabinom_ab", C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     ("ed_plan_ratio_profile", C.c_int, [_vp, _vp, _i64, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     ("ed_plan_ratio_profile_dd", C.c_int, [_vp, _vp, _i64, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("ed_batch_copy_call_ratio_profile", C.c_int, [_vp, _vp, C.c_int, _vp, _i64]),

@@ -367,6 +367,11 @@ class Plan:
         one value per sample (host); mixture: a scalar or one value per sample."""
         return PowerMap(self, test, ref, phi, expected, mixture, layout, stream)
 
+    def quantile_map(self, test, ref, phi, expected, probs=(0.025, 0.975), layout=0, stream=None):
+        """The quantile map of the samples (include/exomedepth_amd.h: ed_plan_quantile_map): a QuantileMap.  Counts, phi and expected as
+        power_map takes them; probs: 1 .. 16 probabilities inside (0, 1), strictly ascending."""
+        return QuantileMap(self, test, ref, phi, expected, probs, layout, stream)
+
     def close(self):
         if self.handle:
             lib().ed_plan_destroy(self.handle)
@@ -1979,6 +1984,145 @@ def detection_power(chrom_off, start, end, test, ref, phi, expected, rows, mixtu
         plan.close()
 
 
+# ---------------------------------------------------------------------------------------------
+# beta-binomial quantiles: qbetabinom, the normal range of every exon and how a region's counts fall into it
+# ---------------------------------------------------------------------------------------------
+def quantile_geometry():
+    """{walk_tile, occupancy_cap, max_total, region_tile, max_probs} of the quantile kernels (ed_quant_geometry)"""
+    out = (C.c_int32 * 5)()
+    check(lib().ed_quant_geometry(out))
+    return dict(zip(("walk_tile", "occupancy_cap", "max_total", "region_tile", "max_probs"), (int(v) for v in out)))
+
+
+def qbetabinom_ab(p, size, shape1, shape2):
+    """reference R/tools.R:42-53 qbetabinom.ab, element by element: with pm the beta-binomial masses of 0 .. size and cs their running
+    sum, above = the first value with cs > p, the result is (above - 1) + (p - cs[above - 1]) / pm[above] (p / pm[0] for the first value).
+    The arguments are recycled to the longest, as R recycles them (on the host); a float64 array of that length (0-d arguments: length
+    1).  NaN (R's NA) where p >= 1, where a shape is not positive and finite, and where size is not a whole number in 0 .. max_total
+    (quantile_geometry)."""
+    args = [_f64(np.atleast_1d(x)).ravel() for x in (p, size, shape1, shape2)]
+    n = 0 if any(a.size == 0 for a in args) else max(a.size for a in args)
+    args = [np.ascontiguousarray(np.resize(a, n)) for a in args]
+    out = np.zeros(n)
+    check(lib().ed_qbetabinom_ab(*[_ptr(a) if n else None for a in args], n, _ptr(out) if n else None))
+    return out
+
+
+def qbetabinom(p, size, phi, prob):
+    """reference R/tools.R:21-25: qbetabinom_ab at shape1 = prob (1 - phi) / phi, shape2 = (1 - prob)(1 - phi) / phi"""
+    phi, prob = _f64(np.atleast_1d(phi)).ravel(), _f64(np.atleast_1d(prob)).ravel()
+    n = 0 if not (phi.size and prob.size) else max(phi.size, prob.size)
+    phi, prob = np.resize(phi, n), np.resize(prob, n)
+    with np.errstate(all="ignore"):
+        a, b = prob * (1. - phi) / phi, (1. - prob) * (1. - phi) / phi
+    return qbetabinom_ab(p, size, a, b)
+
+
+class QuantileMap:
+    """Device-resident quantile map of Plan.quantile_map: per sample the table of (total, q_k, below_k) of its occupied totals at the K
+    requested probabilities, per (sample, exon) the table slot of the exon's total, and the test counts.  q_k = qbetabinom(p_k, total,
+    phi, expected) under the sample's fitted normal state, below_k = the mass strictly below its cut (include/exomedepth_amd.h)."""
+
+    def __init__(self, plan, test, ref, phi, expected, probs=(0.025, 0.975), layout=0, stream=None):
+        self.plan, self.stream = plan, stream
+        phi, expected = _f64(np.atleast_1d(phi)), _f64(np.atleast_1d(expected))
+        S = _n_samples_of(phi)
+        if expected.size != S:
+            raise ValueError("phi and expected must have one value per sample")
+        self.n_samples = S
+        self.probs = _f64(np.atleast_1d(probs)).ravel()
+        on_dev = _is_device(test) and _is_device(ref)
+        if not on_dev and (_is_device(test) or _is_device(ref)):
+            raise ValueError("test and ref must both be device arrays or both be host arrays")
+        self.handle = C.c_void_p()
+        with _staged() as keep:
+            if on_dev:
+                pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
+            else:
+                test, ref = _i32(test), _i32(ref)
+                for x in (test, ref):
+                    _check_counts_shape(x, plan.n_exons, S, layout)
+                pt, pr = _ptr(test), _ptr(ref)
+            check(lib().ed_plan_quantile_map(C.byref(self.handle), plan.handle, pt, pr, int(on_dev), int(layout), _ptr(phi), _ptr(expected),
+                                             _ptr(self.probs) if self.probs.size else None, int(self.probs.size), S, C.c_void_p(stream or 0)))
+
+    def regions(self, rows):
+        """Per (region, sample), a dict of observed (n_regions, n_samples, K + 1) int32: the run's exons per bin, the bin of an exon being
+        the number of k with test count >= ceil(q_k) - 1 (closed below: a count on a cut is in the upper bin); expected (same shape): the
+        sum over the run's exons of the mass the fitted model puts into each bin; n_empty (n_regions, n_samples): the run's exons that
+        read NaN and are in no bin; chi2 (n_regions, n_samples): sum over the bins with expected > 0 of (observed - expected)^2 /
+        expected, on the host -- with a chromosome or the whole exome as the region, the sample's calibration statistic.  rows as
+        PowerMap.regions takes them; a row of (chrom, -1, -1) is a region with no exon inside: zeros."""
+        rows = _region_rows(rows)
+        R, S, KB = rows.size, self.n_samples, self.probs.size + 1
+        none = (rows["start_exon"] == -1) & (rows["end_exon"] == -1)
+        live = np.ascontiguousarray(rows[~none])
+        n = int(live.size)
+        obs, exp, empty = np.zeros((n, S, KB), dtype=np.int32), np.zeros((n, S, KB)), np.zeros((n, S), dtype=np.int32)
+        check(lib().ed_quant_regions(self.handle, _ptr(live), n, _ptr(obs), _ptr(exp), _ptr(empty), C.c_void_p(self.stream or 0)))
+        out = {"observed": np.zeros((R, S, KB), dtype=np.int32), "expected": np.zeros((R, S, KB)), "n_empty": np.zeros((R, S), dtype=np.int32)}
+        at = np.flatnonzero(~none)
+        out["observed"][at], out["expected"][at], out["n_empty"][at] = obs, exp, empty
+        e = out["expected"]
+        with np.errstate(all="ignore"):
+            out["chi2"] = np.sum(np.where(e > 0, (out["observed"] - e) ** 2 / np.where(e > 0, e, 1.0), np.where(np.isnan(e), np.nan, 0.0)), axis=2)
+        return out
+
+    def exons(self):
+        """(2, K, n_samples, n_exons): q, then below, of every exon; NaN where the total was skipped, the sample is outside the model or
+        nothing was crossed"""
+        out = np.zeros((2, self.probs.size, self.n_samples, self.plan.n_exons))
+        check(lib().ed_quant_copy_exons(self.handle, _ptr(out), C.c_void_p(self.stream or 0)))
+        return out
+
+    def table(self, sample):
+        """the sample's table: dict of totals (ascending, int32), q (K, n_totals) and below (K, n_totals)"""
+        n = C.c_int64(0)
+        check(lib().ed_quant_copy_table(self.handle, int(sample), None, None, 0, C.byref(n)))
+        k, K = int(n.value), self.probs.size
+        totals, values = np.zeros(k, dtype=np.int32), np.zeros((2, K, max(k, 1)))
+        if k:
+            check(lib().ed_quant_copy_table(self.handle, int(sample), _ptr(totals), _ptr(values), k, C.byref(n)))
+        return {"totals": totals, "q": values[0, :, :k].copy(), "below": values[1, :, :k].copy()}
+
+    def stats(self):
+        """PowerMap.stats' counters (n_samples .. map_words), n_probs, tiles_walked, tiles_full (what full walks of the same jobs take), and its
+        four times"""
+        cnt, ms = (C.c_int64 * 11)(), (C.c_double * 4)()
+        check(lib().ed_quant_stats(self.handle, cnt, ms))
+        out = dict(zip(("n_samples", "n_exons", "n_jobs", "max_jobs", "n_skipped", "n_bad_samples", "largest_total", "map_words", "n_probs",
+                        "tiles_walked", "tiles_full"), (int(v) for v in cnt)))
+        out.update(zip(("occupancy_ms", "walk_ms", "regions_ms", "exons_ms"), (float(v) for v in ms)))
+        return out
+
+    def free(self):
+        if self.handle:
+            lib().ed_quant_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def normal_range(chrom_off, start, end, test, ref, phi, expected, rows=None, probs=(0.025, 0.975), layout=0, device=0):
+    """The normal range of a cohort: QuantileMap.exons() of the samples' map on a plan of (chrom_off, start, end) -- (2, K, n_samples,
+    n_exons): the quantiles of every exon's test count under its sample's fitted model, then the mass below each -- and, with rows,
+    a pair of that and QuantileMap.regions(rows).  Arguments as Plan and Plan.quantile_map take them."""
+    plan = Plan(chrom_off, start, end, device=device)
+    qm = None
+    try:
+        qm = plan.quantile_map(test, ref, phi, expected, probs, layout)
+        ex = qm.exons()
+        return ex if rows is None else (ex, qm.regions(rows))
+    finally:
+        if qm is not None:
+            qm.free()
+        plan.close()
+
+
 def chromosome_order(chromosome, start, end):
     """Return (order, chrom_levels, chrom_codes_sorted, chrom_off).  Levels are '1'..'22' first (those
     present), then the other names in first-seen order; exons are ordered by (level, midpoint) with
@@ -2268,6 +2412,36 @@ class ExomeDepth:
                               _as_r_integer(self.reference[order]).reshape(n, 1), self.phi[:1], self.expected[:1], rows, mixture=self.prop_tumor,
                               threshold=threshold, transition_probability=transition_probability, expected_CNV_length=expected_CNV_length)
         return out[:, 0]
+
+    def normal_range(self, sequence, xlim, count_threshold=10, probs=(0.025, 0.975)):
+        """The data frame the reference's plot method draws (R/plot_CNVs_method.R:33-63), without the drawing: for the exons of
+        chromosome `sequence` wholly inside xlim whose expected test count (test + reference) * expected exceeds count_threshold, a dict
+        of columns middle, ratio (observed / expected proportion of test reads), test, reference, total_counts, phi, my_min_norm /
+        my_max_norm = qbetabinom(probs[0] / probs[1], total_counts, phi, expected) exon by exon -- a per-exon phi (phi.bins > 1) as the
+        reference takes it (:51) --, my_min_norm_prop / my_max_norm_prop = those over total_counts, and outside (not in the reference):
+        -1 / 0 / +1 where the ratio lies below / inside / above the two proportions over expected, the band the plot draws.  None where
+        no exon is selected (the reference warns and returns NULL).  Needs the annotations CallCNVs stores."""
+        if self.annotations is None:
+            raise ValueError("This function cannot be used if the position of the exons/DNA segments was not included")
+        if len(probs) != 2 or not probs[0] < probs[1]:
+            raise ValueError("probs must be the lower and the upper probability of the band")
+        a = self.annotations
+        total = self.test + self.reference
+        sel = np.flatnonzero((np.asarray(a["chromosome"], dtype=object) == str(sequence)) & (np.asarray(a["start"]) >= xlim[0]) &
+                             (np.asarray(a["end"]) <= xlim[1]) & (total * self.expected > count_threshold))
+        if sel.size == 0:
+            return None
+        test, reference, expected, phi = self.test[sel], self.reference[sel], self.expected[sel], self.phi[sel]
+        out = {"middle": 0.5 * (np.asarray(a["start"], dtype=np.float64)[sel] + np.asarray(a["end"], dtype=np.float64)[sel])}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["ratio"] = (test / (reference + test)) / expected
+            out.update({"test": test, "reference": reference, "total_counts": test + reference, "phi": phi})
+            out["my_min_norm"] = qbetabinom(probs[0], out["total_counts"], phi, expected)
+            out["my_max_norm"] = qbetabinom(probs[1], out["total_counts"], phi, expected)
+            out["my_min_norm_prop"] = out["my_min_norm"] / out["total_counts"]
+            out["my_max_norm_prop"] = out["my_max_norm"] / out["total_counts"]
+            out["outside"] = (out["ratio"] > out["my_max_norm_prop"] / expected).astype(np.int8) - (out["ratio"] < out["my_min_norm_prop"] / expected).astype(np.int8)
+        return out
 
     def AnnotateExtra(self, reference_annotation, min_overlap=0.5, column_name=None):
         """reference R/annotate_extra.R:41-73: adds `column_name` to every row of CNV_calls -- the `names` of the annotation's intervals the

@@ -55,6 +55,7 @@
 #include "ed_hmm_score.hpp"
 #include "ed_mix_plan.hpp"
 #include "ed_power_plan.hpp"
+#include "ed_quant_plan.hpp"
 #include "ed_ratio_plan.hpp"
 #include "ed_rows.hpp"
 
@@ -3001,3 +3002,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edmix.inc"         // (edpost.inc's lse3) behind it for the same reason
 #include "edpower.inc"       // (edrefset.inc's wave sum and scan) last again
 #include "edratio.inc"       // (the call decoration's dd_add) and again
+#include "edquant.inc"       // (edpower.inc's occupancy) and again

@@ -344,15 +344,26 @@ k_pw_price(const ed_call* __restrict__ rows, int64_t R, const double* __restrict
 }  // namespace
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-struct ed_power {
-  const ed_plan* plan = nullptr;
+// What the occupancy passes leave behind for a map's look-ups: per sample the table of its occupied totals and per (sample, exon) the
+// table slot of the exon's total.  The quantile map (edquant.inc) is built on the same.
+struct PwOccupancy {
   int64_t S = 0, E = 0, J = 0;
   int32_t words = 0, largest = 0, max_jobs = 0;
-  int64_t n_skipped = 0, n_bad = 0;
+  int64_t n_skipped = 0;
   std::vector<int64_t> tab_off;      // [S + 1]
   DevBuf<int64_t> d_tab_off;         // [S + 1]
   DevBuf<int32_t> d_slot;            // [S][E]
   DevBuf<int32_t> d_tab_n;           // [J]
+};
+// the job list of a walk, longest first (ed_power_plan.hpp: JobLayout); the walk's own, gone with it
+struct PwJobs {
+  DevBuf<int32_t> d_s, d_n;          // [J] sample, total
+  DevBuf<int64_t> d_dst;             // [J] place in the tables
+};
+
+struct ed_power : PwOccupancy {
+  const ed_plan* plan = nullptr;
+  int64_t n_bad = 0;
   DevBuf<double> d_val;              // [4][J]  mean_del, var_del, mean_dup, var_dup
   double ms[4] = {0, 0, 0, 0};       // occupancy, walk, the last regions call's kernels, the last exon map's kernels
 };
@@ -369,6 +380,85 @@ struct PwClock {
   }
 };
 inline unsigned pw_grid(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, 1 << 20)); }
+
+// host counts go to the device (up_test / up_ref own the copies); test / ref point at the device arrays afterwards
+int pw_stage_counts(const char* entry, const int32_t*& test, const int32_t*& ref, int counts_on_device, int64_t cells, DevBuf<int32_t>& up_test,
+                    DevBuf<int32_t>& up_ref, hipStream_t st)
+{
+  if (counts_on_device || cells <= 0) return ED_OK;
+  if (up_test.alloc((size_t)cells * 4) != hipSuccess || up_ref.alloc((size_t)cells * 4) != hipSuccess)
+    return ed_fail(ED_ERR_NOMEM, "%s: cannot allocate the counts", entry);
+  HIP_TRY(hipMemcpyAsync(up_test.get(), test, (size_t)cells * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(up_ref.get(), ref, (size_t)cells * 4, hipMemcpyHostToDevice, st));
+  test = up_test.get(); ref = up_ref.get();
+  return ED_OK;
+}
+
+// The occupancy passes over DEVICE counts: o (S and E set by the caller) and the job list.  Complete when it returns (it waits for st).
+int pw_occupy(const char* entry, PwOccupancy& o, PwJobs& jobs, const int32_t* test, const int32_t* ref, int layout, hipStream_t st)
+{
+  const int64_t S = o.S, E = o.E, cells = S * E;
+  o.tab_off.assign((size_t)S + 1, 0);
+  auto nomem = [&](const char* what) { return ed_fail(ED_ERR_NOMEM, "%s: cannot allocate %s", entry, what); };
+  DevBuf<int64_t> d_word;       // [0] the largest valid total (int32), [1] the cells skipped
+  if (d_word.alloc(16) != hipSuccess) return nomem("counters");
+  HIP_TRY(hipMemsetAsync(d_word.get(), 0, 16, st));
+  if (cells > 0) {
+    hipLaunchKernelGGL(k_pw_scan, dim3(pw_grid(cells, 256 * 8)), dim3(256), 0, st, test, ref, cells, (int32_t*)d_word.get(),
+                       (unsigned long long*)(d_word.get() + 1));
+    HIP_TRY(hipGetLastError());
+  }
+  int64_t word[2] = {0, 0};
+  if (int rc = ed_d2h(word, d_word.get(), 16, st)) return rc;
+  o.largest = (int32_t)(word[0] & 0xffffffff);
+  o.n_skipped = word[1];
+  const int32_t words = o.words = edpower::map_words(o.largest);
+  DevBuf<unsigned int> d_bits;
+  DevBuf<int32_t> d_prefix, d_count;
+  if (d_bits.alloc((size_t)S * words * 4) != hipSuccess || d_prefix.alloc((size_t)S * words * 4) != hipSuccess ||
+      d_count.alloc((size_t)S * 4) != hipSuccess || o.d_slot.alloc((size_t)std::max<int64_t>(cells, 1) * 4) != hipSuccess ||
+      o.d_tab_off.alloc((size_t)(S + 1) * 8) != hipSuccess)
+    return nomem("the occupancy map");
+  HIP_TRY(hipMemsetAsync(d_bits.get(), 0, (size_t)S * words * 4, st));
+  if (cells > 0) {
+    hipLaunchKernelGGL(k_pw_mark, dim3(pw_grid(cells, 256 * 8)), dim3(256), 0, st, test, ref, cells, layout, E, S, words, d_bits.get());
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_pw_rank, dim3((unsigned)S), dim3(256), 0, st, (const unsigned int*)d_bits.get(), words, d_prefix.get(), d_count.get());
+  HIP_TRY(hipGetLastError());
+  std::vector<int32_t> count((size_t)S);
+  if (int rc = ed_d2h(count.data(), d_count.get(), (size_t)S * 4, st)) return rc;
+  for (int64_t s = 0; s < S; ++s) o.tab_off[(size_t)s + 1] = o.tab_off[(size_t)s] + count[(size_t)s];
+  const edpower::JobLayout lay = edpower::job_layout(count.data(), S);
+  const int64_t J = o.J = lay.n_jobs;
+  o.max_jobs = lay.max_jobs;
+  if (J != o.tab_off[(size_t)S]) return ed_fail(ED_ERR_STATE, "%s: internal error, the job list does not cover the tables", entry);
+  HIP_TRY(hipMemcpyAsync(o.d_tab_off.get(), o.tab_off.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
+  DevBuf<int32_t> d_rank;
+  DevBuf<int64_t> d_off_k;
+  const size_t Ja = (size_t)std::max<int64_t>(J, 1);
+  if (d_rank.alloc((size_t)S * 4) != hipSuccess || d_off_k.alloc(lay.off_k.size() * 8) != hipSuccess || jobs.d_s.alloc(Ja * 4) != hipSuccess ||
+      jobs.d_n.alloc(Ja * 4) != hipSuccess || jobs.d_dst.alloc(Ja * 8) != hipSuccess || o.d_tab_n.alloc(Ja * 4) != hipSuccess)
+    return nomem("the job list");
+  HIP_TRY(hipMemcpyAsync(d_rank.get(), lay.rank.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_off_k.get(), lay.off_k.data(), lay.off_k.size() * 8, hipMemcpyHostToDevice, st));
+  if (J > 0) {
+    hipLaunchKernelGGL(k_pw_jobs, dim3((unsigned)((S * words + 255) / 256)), dim3(256), 0, st, (const unsigned int*)d_bits.get(),
+                       (const int32_t*)d_prefix.get(), (const int32_t*)d_count.get(), words, S, (const int64_t*)o.d_tab_off.get(),
+                       (const int32_t*)d_rank.get(), (const int64_t*)d_off_k.get(), o.d_tab_n.get(), jobs.d_s.get(), jobs.d_n.get(), jobs.d_dst.get());
+    HIP_TRY(hipGetLastError());
+  }
+  if (cells > 0) {
+    constexpr int T = edpower::kSlotTile;
+    if ((S + T - 1) / T > 65535) return ed_fail(ED_ERR_INVALID, "%s: too many samples for one map", entry);
+    hipLaunchKernelGGL(k_pw_slots, dim3((unsigned)((E + T - 1) / T), (unsigned)((S + T - 1) / T)), dim3(256), 0, st, test, ref, layout, E, S, words,
+                       (const unsigned int*)d_bits.get(), (const int32_t*)d_prefix.get(), o.d_slot.get());
+    HIP_TRY(hipGetLastError());
+  }
+  // (the passes read d_bits, d_prefix, d_rank and d_off_k, which go when this returns)
+  HIP_TRY(hipStreamSynchronize(st));
+  return ED_OK;
+}
 }  // namespace
 
 // The map of n_samples samples of the plan's exons.  test / ref: int32 counts, [E][S] (layout 0) or [S][E] (layout 1), on the device
@@ -386,19 +476,13 @@ try {
   if (int rc = require_device()) return rc;
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
-  const int64_t S = n_samples, E = p->E, cells = S * E;
+  const int64_t S = n_samples, E = p->E;
   std::unique_ptr<ed_power> h(new ed_power);
   h->plan = p; h->S = S; h->E = E;
-  h->tab_off.assign((size_t)S + 1, 0);
   auto nomem = [&](const char* what) { return ed_fail(ED_ERR_NOMEM, "ed_plan_power_map: cannot allocate %s", what); };
 
   DevBuf<int32_t> up_test, up_ref;
-  if (!counts_on_device && cells > 0) {
-    if (up_test.alloc((size_t)cells * 4) != hipSuccess || up_ref.alloc((size_t)cells * 4) != hipSuccess) return nomem("the counts");
-    HIP_TRY(hipMemcpyAsync(up_test.get(), test, (size_t)cells * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(up_ref.get(), ref, (size_t)cells * 4, hipMemcpyHostToDevice, st));
-    test = up_test.get(); ref = up_ref.get();
-  }
+  if (int rc = pw_stage_counts("ed_plan_power_map", test, ref, counts_on_device, S * E, up_test, up_ref, st)) return rc;
   // the samples' parameters
   DevBuf<double> d_in, d_par;
   DevBuf<int32_t> d_bad;
@@ -414,70 +498,16 @@ try {
   if (int rc = ed_d2h(bad.data(), d_bad.get(), (size_t)S * 4, st)) return rc;
   for (int32_t b : bad) h->n_bad += b;
 
-  // occupancy
   PwClock clock;
-  DevBuf<int64_t> d_word;       // [0] the largest valid total (int32), [1] the cells skipped
-  if (d_word.alloc(16) != hipSuccess) return nomem("counters");
-  HIP_TRY(hipMemsetAsync(d_word.get(), 0, 16, st));
-  if (cells > 0) {
-    hipLaunchKernelGGL(k_pw_scan, dim3(pw_grid(cells, 256 * 8)), dim3(256), 0, st, test, ref, cells, (int32_t*)d_word.get(),
-                       (unsigned long long*)(d_word.get() + 1));
-    HIP_TRY(hipGetLastError());
-  }
-  int64_t word[2] = {0, 0};
-  if (int rc = ed_d2h(word, d_word.get(), 16, st)) return rc;
-  h->largest = (int32_t)(word[0] & 0xffffffff);
-  h->n_skipped = word[1];
-  const int32_t words = h->words = edpower::map_words(h->largest);
-  DevBuf<unsigned int> d_bits;
-  DevBuf<int32_t> d_prefix, d_count;
-  if (d_bits.alloc((size_t)S * words * 4) != hipSuccess || d_prefix.alloc((size_t)S * words * 4) != hipSuccess ||
-      d_count.alloc((size_t)S * 4) != hipSuccess || h->d_slot.alloc((size_t)std::max<int64_t>(cells, 1) * 4) != hipSuccess ||
-      h->d_tab_off.alloc((size_t)(S + 1) * 8) != hipSuccess)
-    return nomem("the occupancy map");
-  HIP_TRY(hipMemsetAsync(d_bits.get(), 0, (size_t)S * words * 4, st));
-  if (cells > 0) {
-    hipLaunchKernelGGL(k_pw_mark, dim3(pw_grid(cells, 256 * 8)), dim3(256), 0, st, test, ref, cells, layout, E, S, words, d_bits.get());
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_pw_rank, dim3((unsigned)S), dim3(256), 0, st, (const unsigned int*)d_bits.get(), words, d_prefix.get(), d_count.get());
-  HIP_TRY(hipGetLastError());
-  std::vector<int32_t> count((size_t)S);
-  if (int rc = ed_d2h(count.data(), d_count.get(), (size_t)S * 4, st)) return rc;
-  for (int64_t s = 0; s < S; ++s) h->tab_off[(size_t)s + 1] = h->tab_off[(size_t)s] + count[(size_t)s];
-  const edpower::JobLayout lay = edpower::job_layout(count.data(), S);
-  const int64_t J = h->J = lay.n_jobs;
-  h->max_jobs = lay.max_jobs;
-  if (J != h->tab_off[(size_t)S]) return ed_fail(ED_ERR_STATE, "ed_plan_power_map: internal error, the job list does not cover the tables");
-  HIP_TRY(hipMemcpyAsync(h->d_tab_off.get(), h->tab_off.data(), (size_t)(S + 1) * 8, hipMemcpyHostToDevice, st));
-  DevBuf<int32_t> d_rank, d_job_s, d_job_n;
-  DevBuf<int64_t> d_off_k, d_job_dst;
-  const size_t Ja = (size_t)std::max<int64_t>(J, 1);
-  if (d_rank.alloc((size_t)S * 4) != hipSuccess || d_off_k.alloc(lay.off_k.size() * 8) != hipSuccess || d_job_s.alloc(Ja * 4) != hipSuccess ||
-      d_job_n.alloc(Ja * 4) != hipSuccess || d_job_dst.alloc(Ja * 8) != hipSuccess || h->d_tab_n.alloc(Ja * 4) != hipSuccess ||
-      h->d_val.alloc(Ja * 4 * 8) != hipSuccess)
-    return nomem("the job list");
-  HIP_TRY(hipMemcpyAsync(d_rank.get(), lay.rank.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_off_k.get(), lay.off_k.data(), lay.off_k.size() * 8, hipMemcpyHostToDevice, st));
-  if (J > 0) {
-    hipLaunchKernelGGL(k_pw_jobs, dim3((unsigned)((S * words + 255) / 256)), dim3(256), 0, st, (const unsigned int*)d_bits.get(),
-                       (const int32_t*)d_prefix.get(), (const int32_t*)d_count.get(), words, S, (const int64_t*)h->d_tab_off.get(),
-                       (const int32_t*)d_rank.get(), (const int64_t*)d_off_k.get(), h->d_tab_n.get(), d_job_s.get(), d_job_n.get(), d_job_dst.get());
-    HIP_TRY(hipGetLastError());
-  }
-  if (cells > 0) {
-    constexpr int T = edpower::kSlotTile;
-    if ((S + T - 1) / T > 65535) return ed_fail(ED_ERR_INVALID, "ed_plan_power_map: too many samples for one map");
-    hipLaunchKernelGGL(k_pw_slots, dim3((unsigned)((E + T - 1) / T), (unsigned)((S + T - 1) / T)), dim3(256), 0, st, test, ref, layout, E, S, words,
-                       (const unsigned int*)d_bits.get(), (const int32_t*)d_prefix.get(), h->d_slot.get());
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(st));
+  PwJobs jobs;
+  if (int rc = pw_occupy("ed_plan_power_map", *h, jobs, test, ref, layout, st)) return rc;
+  const int64_t J = h->J;
+  if (h->d_val.alloc((size_t)std::max<int64_t>(J, 1) * 4 * 8) != hipSuccess) return nomem("the tables");
   h->ms[0] = clock.lap();
   // the walk
   if (J > 0) {
     hipLaunchKernelGGL(k_pw_walk, dim3((unsigned)((J + edpower::kWalkWaves - 1) / edpower::kWalkWaves)), dim3(edpower::kWalkWaves * 64), 0, st,
-                       (const int32_t*)d_job_s.get(), (const int32_t*)d_job_n.get(), (const int64_t*)d_job_dst.get(), J, (const double*)d_par.get(),
+                       (const int32_t*)jobs.d_s.get(), (const int32_t*)jobs.d_n.get(), (const int64_t*)jobs.d_dst.get(), J, (const double*)d_par.get(),
                        (const int32_t*)d_bad.get(), S, h->d_val.get());
     HIP_TRY(hipGetLastError());
   }

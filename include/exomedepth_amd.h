@@ -420,6 +420,47 @@ int ed_power_copy_table(const ed_power* map, int64_t sample, int32_t* totals, do
 int ed_power_stats(const ed_power* map, int64_t counts[8], double ms[4]);
 int ed_power_geometry(int32_t out[4]);
 
+/* ---- the quantile map: qbetabinom of every exon under the fitted normal state, and how a region's counts fall between the quantiles ----
+ * qbetabinom.ab of the reference (R/tools.R:42-53), on which its plot method builds the band of every exon (R/plot_CNVs_method.R:54-63).
+ * For a size n, shapes (a, b) and a probability p: pm[x] = the beta-binomial mass at x = 0 .. n, C(x) = pm[0] + .. + pm[x], cut = the
+ * smallest x with C(x) > p,
+ *   q = cut + (p - C(cut - 1)) / pm[cut]     (C(-1) = 0: q = p / pm[0] for cut = 0)          below = C(cut - 1)
+ * No x with C(x) > p (p >= 1, or p within rounding of 1): NaN -- R's NA -- in both.  n = 0: q = p, below = 0.
+ * q inverts the piecewise-linear G(q) = C(x - 1) + (q - x) pm[x], x < q <= x + 1: it is continuous in the masses, the cut is not.
+ * Sample s has a = expected (1 - phi) / phi, b = (1 - expected)(1 - phi) / phi, in qbetabinom's operation order (R/tools.R:22-23; the
+ * normal state only, no mixture).  q and below depend on the exon through its total alone: the map walks every sample once per OCCUPIED
+ * total, as the detection-power map does and with its occupancy map, job list and skipping rules (a total above ed_quant_geometry's
+ * largest, or a sum below 0, reads NaN and is counted; so does every exon of a sample whose shapes are not positive and finite).  A walk
+ * ends where its last probability is crossed.  The bits of a table value depend on (n, phi, expected, p) alone -- not on the other
+ * probabilities, the number of samples, the other samples, the layout or the order of the jobs.
+ * ed_plan_quantile_map: counts as ed_plan_power_map reads them; phi, expected: HOST double [n_samples]; probs: HOST double [n_probs], 1 ..
+ *   16 of them, finite, inside (0, 1), strictly ascending.  The plan gives the exons and checks region rows.  Complete on return; the
+ *   counts are not needed afterwards.  The plan must outlive the map.  ED_ERR_INVALID before anything is enqueued: a NULL pointer, a
+ *   layout other than 0 / 1, n_samples outside 1 .. 2^20, a bad list of probabilities.
+ * ed_quant_regions: rows as ed_power_regions reads and checks them.  With cut_k = ceil(q_k) - 1 (q_k > 0; NaN: no cut), the bin of an exon
+ *   is the number of k with test count >= cut_k: bins are closed below, a count on a cut belongs to the upper bin.  HOST outputs:
+ *   observed [n_rows][n_samples][K + 1] = the run's exons per bin; expected [n_rows][n_samples][K + 1] = the sum over the run's exons of
+ *   below_{b+1} - below_b (below_0 = 0, below_{K+1} = 1), in ed_power_regions' order of sums; n_empty [n_rows][n_samples] = the exons
+ *   that read NaN, which are in no bin.
+ * ed_quant_copy_exons: HOST double [2][K][n_samples][n_exons]: q, then below.
+ * ed_quant_copy_table: one sample's table: *n = its occupied totals; when cap >= *n also totals [*n] (ascending) and values [2][K][cap].
+ * ed_quant_stats: counts = ed_power_stats' eight, then {probabilities, tiles walked, tiles that full walks of the same jobs take}; ms as
+ *   ed_power_stats.
+ * ed_quant_geometry: out = ed_power_geometry's four, then the most probabilities of one request.
+ * ed_qbetabinom_ab: qbetabinom.ab element by element over HOST arrays of length n: the map's walk with one probability, and the map's bits
+ *   for the same (size, shapes, p).  NaN: p >= 1, shapes that are not positive and finite, a size that is not a whole number in 0 .. the
+ *   largest total walked. */
+typedef struct ed_quant ed_quant;
+int ed_plan_quantile_map(ed_quant** map, const ed_plan* plan, const int32_t* test, const int32_t* ref, int counts_on_device, int layout,
+                         const double* phi, const double* expected, const double* probs, int n_probs, int64_t n_samples, void* stream);
+void ed_quant_free(ed_quant* map);
+int ed_quant_regions(ed_quant* map, const ed_call* rows, int64_t n_rows, int32_t* observed, double* expected, int32_t* n_empty, void* stream);
+int ed_quant_copy_exons(ed_quant* map, double* out, void* stream);
+int ed_quant_copy_table(const ed_quant* map, int64_t sample, int32_t* totals, double* values, int64_t cap, int64_t* n);
+int ed_quant_stats(const ed_quant* map, int64_t counts[11], double ms[4]);
+int ed_quant_geometry(int32_t out[5]);
+int ed_qbetabinom_ab(const double* p, const double* size, const double* shape1, const double* shape2, int64_t n, double* out);
+
 /* ---- the copy-ratio profile: how many copies is a call? ----
  * The HMM's states stand for the copy ratios 0.5, 1 and 1.5; the beta-binomial emission is defined for any.  For a row (sample s, exons
  * start_exon .. end_exon, global indices as in ed_call) and a DOSE mu, -2 < mu <= 2 -- the copy ratio is r = 1 + mu / 2 --
