@@ -181,6 +181,18 @@ SYMBOLS = [
     ("ed_readcount_kernel_ms", C.c_int, [_vp, C.POINTER(_dbl), C.POINTER(_dbl)]),
     ("ed_readcount_geometry", C.c_int, [C.POINTER(_i32)]),
     ("ed_bam_scan_records", C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    ("ed_bamdev_create", C.c_int, [C.POINTER(_vp), C.c_int, _i64]),
+    ("ed_bamdev_destroy", None, [_vp]),
+    ("ed_bamdev_begin", C.c_int, [_vp, _i64]),
+    ("ed_bamdev_set_guard_gap", C.c_int, [_vp, _i32]),
+    ("ed_bamdev_records", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_vp)]),
+    ("ed_readcount_add_device", C.c_int, [_vp, _i32, C.c_int, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),
+    ("ed_bamdev_push", C.c_int, [_vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    ("ed_bamdev_end", C.c_int, [_vp]),
+    ("ed_bamdev_block_status", C.c_int, [_vp, _i64, _vp, C.POINTER(_i64)]),
+    ("ed_bamdev_copy_inflated", C.c_int, [_vp, _vp, _i64, C.POINTER(_i64)]),
+    ("ed_bamdev_kernel_ms", C.c_int, [_vp, C.POINTER(_dbl)]),
+    ("ed_bamdev_geometry", C.c_int, [C.POINTER(_i32)]),
     ("ed_plan_posterior", C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     ("ed_plan_call_posterior", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("ed_batch_copy_posterior", C.c_int, [_vp, _vp]),

@@ -3088,6 +3088,14 @@ class ReadCounter:
         check(lib().ed_readcount_add(self.handle, int(column), int(mode), int(refid.size), _ptr(refid), _ptr(pos), _ptr(tlen), _ptr(fm),
                                      int(r2c.size), _ptr(r2c) if r2c.size else None, int(min_mapq), int(read_width)))
 
+    def add_device(self, column, device_records, ref_names, mode=0, min_mapq=20, read_width=300):
+        """add() for records that are on the device already (bam.DeviceRecords, from DeviceBamFile.batches()): ed_readcount_add_device"""
+        self._open()
+        r2c = self.ref_to_chrom(ref_names)
+        p = [C.c_void_p(x) for x in device_records.ptrs]
+        check(lib().ed_readcount_add_device(self.handle, int(column), int(mode), int(device_records.n), p[0], p[1], p[2], p[3], int(r2c.size),
+                                            _ptr(r2c) if r2c.size else None, int(min_mapq), int(read_width), None))
+
     def finish(self, column):
         self._open()
         check(lib().ed_readcount_finish(self.handle, int(column)))
@@ -3174,8 +3182,10 @@ def bed_targets(bed_frame=None, bed_file=None, include_chr=False, reorder=True):
     return out
 
 
-def _count_bams(frame, bam_files, mode, min_mapq, read_width, device):
+def _count_bams(frame, bam_files, mode, min_mapq, read_width, device, inflate="host"):
     from . import bam as _bam
+    if inflate not in ("host", "device"):
+        raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
     bam_files = [bam_files] if isinstance(bam_files, (str, bytes)) or hasattr(bam_files, "__fspath__") else list(bam_files)
     if not bam_files:
         raise ValueError("bam_files is empty")
@@ -3197,6 +3207,12 @@ def _count_bams(frame, bam_files, mode, min_mapq, read_width, device):
         rc = ReadCounter(frame["chromosome"], frame["start"], frame["end"], len(bam_files), device=device)
         try:
             for col, path in enumerate(bam_files):
+                if inflate == "device":              # the file crosses the link compressed; its record fields never visit the host
+                    b = _bam.DeviceBamFile(path, device=device)
+                    for rec in b.batches():
+                        rc.add_device(col, rec, b.ref_names, mode=mode, min_mapq=min_mapq, read_width=read_width)
+                    rc.finish(col)
+                    continue
                 with _bam.BamFile(path, pool) as b:
                     for rec in b.chunks():           # the kernels of one chunk run while the next is inflated and scanned
                         rc.add(col, rec, b.ref_names, mode=mode, min_mapq=min_mapq, read_width=read_width)
@@ -3210,18 +3226,21 @@ def _count_bams(frame, bam_files, mode, min_mapq, read_width, device):
     return out
 
 
-def getBamCounts(bed_frame=None, bed_file=None, bam_files=(), index_files=None, min_mapq=20, read_width=300, include_chr=False, device=0):
+def getBamCounts(bed_frame=None, bed_file=None, bam_files=(), index_files=None, min_mapq=20, read_width=300, include_chr=False, device=0,
+                 inflate="host"):
     """reference R/countBamInGranges.R:298-370: the exon x sample count frame from BAM files and a BED frame, counted on the device.
     Returns a dict of columns in the reference's order -- chromosome, start (BED start + 1), end, exon when the frame has a fourth text column,
     then one int32 array per basename(bam) -- with rows in the reference's order (bed_targets).  A fragment per record as include/exomedepth_amd.h
     states it ("Reads per exon", mode 0); every target chromosome must be named in each BAM header (ValueError).  index_files is accepted and
-    ignored: the whole file is scanned, which gives the same counts.  GC content (referenceFasta) is not computed."""
+    ignored: the whole file is scanned, which gives the same counts.  GC content (referenceFasta) is not computed.
+    inflate: "host" (the default) inflates the files' BGZF blocks on the host's thread pool; "device" sends them to the device compressed and
+    inflates, scans and gathers them there (bam.DeviceBamFile, ReadCounter.add_device) -- the same frame and the same errors for the same files; the headers are checked on the host first."""
     frame = bed_targets(bed_frame, bed_file, include_chr=include_chr, reorder=True)
-    return _count_bams(frame, bam_files, 0, min_mapq, read_width, device)
+    return _count_bams(frame, bam_files, 0, min_mapq, read_width, device, inflate)
 
 
-def count_everted_reads(bed_frame=None, bed_file=None, bam_files=(), index_files=None, min_mapq=20, include_chr=False, device=0):
+def count_everted_reads(bed_frame=None, bed_file=None, bam_files=(), index_files=None, min_mapq=20, include_chr=False, device=0, inflate="host"):
     """reference R/countBamInGranges.R:424-468: everted read pairs (duplication evidence) per region; as getBamCounts, but the rows keep
-    the caller's order and the rule is the everted one (mode 1: mapq >= min_mapq)."""
+    the caller's order and the rule is the everted one (mode 1: mapq >= min_mapq); inflate as there."""
     frame = bed_targets(bed_frame, bed_file, include_chr=include_chr, reorder=False)
-    return _count_bams(frame, bam_files, 1, min_mapq, 0, device)
+    return _count_bams(frame, bam_files, 1, min_mapq, 0, device, inflate)

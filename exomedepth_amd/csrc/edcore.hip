@@ -51,6 +51,7 @@
 #include "ed_dtab.h"
 #include "ed_own.hpp"
 #include "ed_bamscan.hpp"
+#include "ed_inflate.hpp"
 #include "ed_launch_plan.hpp"
 #include "ed_hmm_score.hpp"
 #include "ed_mix_plan.hpp"
@@ -3003,3 +3004,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edpower.inc"       // (edrefset.inc's wave sum and scan) last again
 #include "edratio.inc"       // (the call decoration's dd_add) and again
 #include "edquant.inc"       // (edpower.inc's occupancy) and again
+#include "edinflate.inc"     // (nothing of the others) last, for the same reason

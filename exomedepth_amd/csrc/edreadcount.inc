@@ -198,6 +198,8 @@ struct ed_readcount {
   DevBuf<int32_t> d_counts;    // [n_columns][n]
   RcntSet set[2];
   Event f0, f1;                // around k_rcnt_finish
+  DevBuf<int32_t> d_r2c;       // ed_readcount_add_device: the refID table
+  Event dev_ready;             // ... and the caller's stream at the time of the call
   Stream copy, stream;         // (declared last: they go first, after ed_readcount_destroy has waited for them)
 };
 
@@ -395,6 +397,42 @@ try {
   return ED_OK;
 }
 ED_CATCH("ed_readcount_add")
+
+// ed_readcount_add with the four arrays already on the DEVICE, ordered behind ready_stream (what the caller queued there before the call is complete
+// before the arrays are read).  The same kernel, the same refusals, the same one-column-at-a-time state; the arrays have been read when it returns.
+ED_EXPORT int ed_readcount_add_device(ed_readcount* a, int32_t column, int mode, int64_t n_records, const int32_t* d_refid, const int32_t* d_pos,
+                                      const int32_t* d_tlen, const uint32_t* d_flag_mapq, int32_t n_ref, const int32_t* ref_to_chrom, int32_t min_mapq,
+                                      int32_t read_width, void* ready_stream)
+try {
+  if (!a || n_records < 0 || n_ref < 0 || (n_records > 0 && (!d_refid || !d_pos || !d_tlen || !d_flag_mapq)) || (n_ref > 0 && !ref_to_chrom))
+    return ed_fail(ED_ERR_INVALID, "ed_readcount_add_device: bad arguments");
+  if (column < 0 || column >= a->n_columns)
+    return ed_fail(ED_ERR_INVALID, "ed_readcount_add_device: column %d outside 0 .. %d", column, a->n_columns - 1);
+  if (mode != 0 && mode != 1) return ed_fail(ED_ERR_INVALID, "ed_readcount_add_device: mode %d (0 = getBamCounts' rule, 1 = everted reads)", mode);
+  if (read_width < 0) return ed_fail(ED_ERR_INVALID, "ed_readcount_add_device: read_width %d < 0", read_width);
+  for (int32_t r = 0; r < n_ref; ++r)
+    if (ref_to_chrom[r] < -1 || ref_to_chrom[r] >= a->n_chrom)
+      return ed_fail(ED_ERR_INVALID, "ed_readcount_add_device: ref_to_chrom[%d] = %d outside -1 .. %d", r, ref_to_chrom[r], a->n_chrom - 1);
+  if (a->pending >= 0 && a->pending != column)
+    return ed_fail(ED_ERR_STATE, "ed_readcount_add_device: column %d has chunks added and is not finished (ed_readcount_finish); the histograms serve "
+                   "one column at a time", a->pending);
+  HIP_TRY(hipSetDevice(a->device));
+  if (n_records == 0 || a->n == 0 || n_ref == 0) return ED_OK;
+  if (n_records > (int64_t)2147483647 * kRcntPerGroup) return ed_fail(ED_ERR_INVALID, "ed_readcount_add_device: too many records for one launch");
+  if (a->d_r2c.reserve((size_t)n_ref * 4) != hipSuccess) return ed_fail(ED_ERR_NOMEM, "ed_readcount_add_device: device allocation failed");
+  if (!a->dev_ready) HIP_TRY(a->dev_ready.create(hipEventDisableTiming));
+  a->pending = column;
+  HIP_TRY(hipMemcpyAsync(a->d_r2c.get(), ref_to_chrom, (size_t)n_ref * 4, hipMemcpyHostToDevice, a->stream));
+  HIP_TRY(hipEventRecord(a->dev_ready, (hipStream_t)ready_stream));
+  HIP_TRY(hipStreamWaitEvent(a->stream, a->dev_ready, 0));
+  unsigned int* histA = a->d_hist;
+  hipLaunchKernelGGL(k_rcnt_bin, dim3((unsigned int)((n_records + kRcntPerGroup - 1) / kRcntPerGroup)), dim3(kRcntBlock), 0, a->stream, a->table, d_refid,
+                     d_pos, d_tlen, d_flag_mapq, n_records, (const int32_t*)a->d_r2c.get(), n_ref, mode, min_mapq, read_width, histA, histA + a->n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(a->stream));             // the caller's arrays (a bamdev batch's) are free again
+  return ED_OK;
+}
+ED_CATCH("ed_readcount_add_device")
 
 ED_EXPORT int ed_readcount_finish(ed_readcount* a, int32_t column)
 try {

@@ -1090,6 +1090,57 @@ int ed_readcount_geometry(int32_t out[4]);
 int ed_bam_scan_records(const uint8_t* buf, int64_t n_bytes, int64_t cap, int32_t* refid, int32_t* pos, int32_t* tlen, uint32_t* flag_mapq,
                         int64_t* n_records, int64_t* bytes_consumed);
 
+/* =====================================================================================
+ * BAM files on the device: BGZF blocks inflated and CRC-checked by the GPU -- csrc/edinflate.inc, csrc/ed_inflate.hpp
+ * ===================================================================================== */
+
+/* A BGZF file crosses the link compressed: ed_bamdev_push takes a piece of the file, cuts the whole BGZF blocks off its front (the rules of
+ * the gzip header and its BC subfield; at most batch_bytes of them, one at least), uploads them and inflates them, one wavefront a block
+ * (k_bgzf_inflate), into ONE contiguous device buffer -- every block's place is known from the ISIZE words before anything is decoded.  A block
+ * is accepted if and only if zlib accepts its DEFLATE stream and its own CRC-32 and ISIZE confirm the bytes; each block gets a status:
+ *   0 OK  1 BAD_HEADER  2 BAD_BTYPE  3 BAD_STORED_LEN  4 BAD_CODE_LENGTHS  5 BAD_SYMBOL  6 BAD_DISTANCE  7 OUTPUT_OVERRUN  8 INPUT_OVERRUN
+ *   9 SIZE_MISMATCH  10 BAD_CRC
+ * and a bad block leaves its neighbours' bytes and statuses alone.  Two batches are in flight: a push stages and uploads its batch under the kernel
+ * of the batch before, then waits for THAT batch only, so a block that does not inflate fails the call that waits for its batch -- the next
+ * ed_bamdev_push or ed_bamdev_end -- with ED_ERR_INVALID and a message that names the block's index in the file, its byte offset and its status.
+ * Refused before any device work: bytes that are no BGZF header (ED_ERR_INVALID), a block whose ISIZE is above 65536.
+ * ed_bamdev_begin starts a file (block, byte and record counts from zero).  *bytes_consumed is what the call took off the front of
+ * buf; the caller carries the rest (an incomplete block) into its next piece.  ed_bamdev_block_status / ed_bamdev_copy_inflated: the statuses and
+ * the inflated bytes of the last batch waited for, whether it was good or not.  An object is not for two threads at a time; it sets its device on every call.
+ */
+typedef struct ed_bamdev ed_bamdev;
+int ed_bamdev_create(ed_bamdev** b, int device, int64_t batch_bytes);
+void ed_bamdev_destroy(ed_bamdev* b);
+/* first_record_offset: where the first alignment record begins in the inflated stream (the length of the BAM header, which the caller parses from
+ * the first blocks), or < 0 to inflate only.  With an offset every batch's records are scanned and gathered on the device (k_bam_scan_blocks,
+ * k_bam_scan_chain, k_bam_gather): refID, pos, tlen and flag | mapq << 16, element for element what ed_bam_scan_records gives for the same stream.
+ * A record cut by the end of a batch is carried, device to device, in front of the next batch's stream.  A block_size word below 32 or above 2^28
+ * fails the call that waits for its batch with ED_ERR_INVALID, naming the record's index in the file, the word's byte offset in the record stream
+ * and its value, as ed_bam_scan_records does; the records before it are delivered (ed_bamdev_records).  Bytes of an incomplete record left at
+ * ed_bamdev_end: ED_ERR_INVALID, "truncated BAM". */
+int ed_bamdev_begin(ed_bamdev* b, int64_t first_record_offset);
+/* *n_records: the records of the batch this call waited for (the one pushed before), 0 when it waited for none */
+int ed_bamdev_push(ed_bamdev* b, const uint8_t* buf, int64_t n_bytes, int64_t* bytes_consumed, int64_t* n_records);
+int ed_bamdev_end(ed_bamdev* b);
+/* the four DEVICE arrays of the last batch waited for (refID, pos, tlen: int32; flag | mapq << 16: uint32), *n records each; they stand until
+ * the second push after the one that waited for them */
+int ed_bamdev_records(ed_bamdev* b, int64_t* n, void* d_ptrs[4]);
+int ed_bamdev_block_status(ed_bamdev* b, int64_t cap, int32_t* status, int64_t* n_blocks);
+int ed_bamdev_copy_inflated(ed_bamdev* b, uint8_t* out, int64_t cap, int64_t* n);
+/* device milliseconds so far: out = {k_bgzf_inflate, k_bam_scan_blocks + k_bam_scan_chain, k_bam_gather} */
+int ed_bamdev_kernel_ms(ed_bamdev* b, double out[3]);
+/* for tests, between ed_bamdev_begin and the first push: `gap` guard bytes before, between and after the blocks' output slots
+ * (ed_bamdev_copy_inflated then returns slots and guards as they lie; the stream is not contiguous, so nothing is scanned) */
+int ed_bamdev_set_guard_gap(ed_bamdev* b, int32_t gap);
+/* Launch geometry, for tests that place their shapes on its edges: out = {BGZF blocks (wavefronts) of a workgroup of k_bgzf_inflate, its threads,
+ * bytes of LDS decode tables a block takes, BGZF blocks (lanes) of a workgroup of the scan and the gather}.  No result depends on them. */
+int ed_bamdev_geometry(int32_t out[4]);
+/* ed_readcount_add with the four record arrays already on the DEVICE (ed_bamdev_records), ordered behind ready_stream (NULL: the null stream): the
+ * same kernel, the same refusals, the same one-column-at-a-time state.  ref_to_chrom is a HOST array.  The arrays have been read on return. */
+int ed_readcount_add_device(ed_readcount* rc, int32_t column, int mode, int64_t n_records, const int32_t* d_refid, const int32_t* d_pos,
+                            const int32_t* d_tlen, const uint32_t* d_flag_mapq, int32_t n_ref, const int32_t* ref_to_chrom, int32_t min_mapq,
+                            int32_t read_width, void* ready_stream);
+
 /* ---- utilities ---- */
 /* device memory through the library, for callers without a HIP binding (tests, R shim) */
 int ed_malloc(void** dptr, size_t bytes);
