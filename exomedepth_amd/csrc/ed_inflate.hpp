@@ -6,7 +6,8 @@
 // zlib's inflate (raw, 32 KiB window) accepts and the block's own CRC-32 and ISIZE confirm.  Like _inflate it reads of the gzip header only XLEN,
 // and ignores what follows the final DEFLATE block.
 //
-// The decoder is a template over its executor W: Serial (one thread; the plain inflate_block below) or the kernel's Wave (64 lanes).  The symbol
+// The decoder is a template over its executor W: Serial (one thread; the plain inflate_block below) or Lanes<P> (the kernel's 64 lanes of a
+// wavefront; tools/inflate_lanes_check.cpp's emulated ones).  The symbol
 // loop is the same for every lane of an executor; what the lanes share out is marked by loops of the form
 //   for (i = w.lane(); i < n; i += w.lanes())
 // and a w.sync() stands wherever a lane reads what another lane wrote (nothing for Serial).  Every loop consumes at least one input bit or one
@@ -287,6 +288,34 @@ struct Serial {
   ED_INF_HD void flush() {}
   ED_INF_HD bool literal(uint32_t b) { if (pos >= cap) return false; out[pos++] = (uint8_t)b; return true; }
   ED_INF_HD uint32_t xor_all(uint32_t v) const { return v; }
+};
+
+// P::kLanes lanes, one value of this type a lane.  Literals are collected a lane each (lane k holds the k-th pending one) and stored kLanes at a
+// time, or when a copy needs them in place (flush).  pos counts the pending literals too; np and mine are the same in every lane at every step,
+// so no lane waits for another here.  The primitive P supplies what the machine has: kLanes, sync() -- a barrier of the lanes after which each
+// sees what the others wrote before it -- and xor_all(v), the XOR of every lane's v, called by all lanes.  The kernel's is in edinflate.inc
+// (a wavefront); tools/inflate_lanes_check.cpp runs this text on emulated lanes under adversarial schedules.
+template <class P>
+struct Lanes {
+  uint8_t* out;
+  uint32_t pos, cap;
+  const uint32_t* crc_tab;
+  int ln;
+  uint32_t np, mine;           // literals collected and not stored yet; this lane's
+  P prim;
+  ED_INF_HD int lane() const { return ln; }
+  ED_INF_HD int lanes() const { return P::kLanes; }
+  ED_INF_HD void sync() { prim.sync(); }
+  ED_INF_HD void flush() { if ((uint32_t)ln < np) out[pos - np + (uint32_t)ln] = (uint8_t)mine; np = 0; }
+  ED_INF_HD bool literal(uint32_t b)
+  {
+    if (pos >= cap) return false;
+    if ((uint32_t)ln == np) mine = b;
+    ++np; ++pos;
+    if (np == (uint32_t)P::kLanes) flush();
+    return true;
+  }
+  ED_INF_HD uint32_t xor_all(uint32_t v) { return prim.xor_all(v); }
 };
 
 // len bytes from `dist` back.  With dist < len the source is periodic, so every byte is read from what lay there before the copy began.

@@ -11,7 +11,7 @@
 // the same wavefront stored a few instructions earlier.  That is correct because (1) one wavefront's vector memory instructions are issued in
 // program order to one vector L1, which serves a load behind the stores that precede it, so a load sees every earlier store of its own wavefront
 // (the AMDGPU memory model needs no cache action and no wait for wavefront-scope synchronisation for that reason), and (2) the compiler is kept from
-// moving the load above those stores by a wavefront-scope acquire-release fence (InfWave::sync) between every store and a dependent load -- before
+// moving the load above those stores by a wavefront-scope acquire-release fence (InfWavePrim::sync) between every store and a dependent load -- before
 // each match copy, before the CRC pass, around the table building.  No other wavefront ever touches the slot.  LDS then holds only the decode
 // tables (edinf::Tables, 3.9 KiB a wavefront): a 64 KiB window in LDS would let two blocks decode on a CU instead of the 16 the kernel's registers allow.
 //
@@ -40,30 +40,16 @@ constexpr int32_t kInfGuardWord = (int32_t)0xa5a5a5a5;
 
 struct InfJob { int64_t out_off; uint32_t in_off, in_len, isize, pad; };
 
-struct InfWave {               // the 64-lane executor of edinf::inflate_stream
-  uint8_t* out;
-  uint32_t pos, cap;
-  const uint32_t* crc_tab;
-  int ln;
-  uint32_t np, mine;           // literals collected and not stored yet (lane k holds the k-th)
-  __device__ int lane() const { return ln; }
-  __device__ int lanes() const { return 64; }
+struct InfWavePrim {           // what a wavefront gives edinf::Lanes, the 64-lane executor of edinf::inflate_stream (ed_inflate.hpp)
+  static constexpr int kLanes = 64;
   __device__ void sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-  __device__ void flush() { if ((uint32_t)ln < np) out[pos - np + (uint32_t)ln] = (uint8_t)mine; np = 0; }
-  __device__ bool literal(uint32_t b)
-  {
-    if (pos >= cap) return false;
-    if ((uint32_t)ln == np) mine = b;
-    ++np; ++pos;
-    if (np == 64) flush();
-    return true;
-  }
   __device__ uint32_t xor_all(uint32_t v) const
   {
     for (int d = 32; d; d >>= 1) v ^= (uint32_t)__shfl_xor((int)v, d, 64);
     return v;
   }
 };
+using InfWave = edinf::Lanes<InfWavePrim>;
 
 static_assert(kInfBlock == 256, "k_bgzf_inflate fills the CRC table an entry a thread");
 
@@ -84,7 +70,7 @@ k_bgzf_inflate(const uint8_t* __restrict__ in, const InfJob* __restrict__ jobs, 
   int st = edinf::block_info(blk, j.in_len, &bi);
   if (st == edinf::OK && bi.isize != j.isize) st = edinf::SIZE_MISMATCH;      // (the host read the same bytes: it cannot differ)
   if (st == edinf::OK) {
-    InfWave w{out + j.out_off, 0u, j.isize, crc_tab, (int)(threadIdx.x & 63), 0u, 0u};
+    InfWave w{out + j.out_off, 0u, j.isize, crc_tab, (int)(threadIdx.x & 63), 0u, 0u, InfWavePrim{}};
     edinf::Report rep{0, 0};
     st = edinf::inflate_stream(w, tabs[wv], blk + bi.data_off, bi.data_len, bi.crc, rep);
   }

@@ -371,3 +371,161 @@ def test_add_device_equals_host_fed_matrix(bam, written):
                 rc.add_device(5, bam.DeviceRecords(None, 1, (8, 8, 8, 8)), f.ref_names)
         finally:
             rc.close()
+
+
+# ------------------------------------------------------------------------------------------------ the 64-lane executor at its edges
+@pytest.fixture(scope="module")
+def lane():
+    return ic.lane_cases()
+
+
+@pytest.mark.parametrize("order", ["forward", "reversed", "on every wavefront"])
+def test_lane_edges(bam, lane, order):
+    """the hand-made blocks of inflate_cases.lane_cases (pending literals x distance x length, dependent chains, mixed block types, tables zlib
+    never writes, ISIZE at the CRC slices' edges) against zlib's bytes, with guard bytes around every slot; in both orders, and each block four
+    times in a row, so that it is decoded by each of the workgroup's wavefronts"""
+    w = bam.bamdev_geometry()["blocks_per_workgroup"]
+    cases = {"forward": list(lane), "reversed": list(lane)[::-1], "on every wavefront": [c for c in lane for _ in range(w)]}[order]
+    assert len(ic.triples()) >= 1500 and w >= 4
+    err, status, raw = _run(bam, [b for _, b, _ in cases])
+    assert err is None
+    assert status.size == len(cases) and (status == 0).all(), [(cases[k][0], bam.INFLATE_STATUS[s]) for k, s in enumerate(status) if s]
+    got = _slots(raw, [len(p) for _, _, p in cases])
+    for k, ((name, _, p), g) in enumerate(zip(cases, got)):
+        assert g == p, (name, k)
+
+
+def test_lane_refusals(bam, lane):
+    """inflate_cases.lane_bad_blocks among good blocks: each bad one gets the status it is listed with, each neighbour its bytes, the guard bytes
+    stand, and the call that waits for the batch names the first bad block"""
+    bad = ic.lane_bad_blocks()
+    some = [c for c in lane if len(c[1]) < 4000]
+    rows = []                                               # (name, block, payload or None, status name)
+    for k, (name, b, st) in enumerate(bad):
+        rows.append(some[k % len(some)] + (None,))
+        rows.append((name, b, None, st))
+    rows.append(some[0] + (None,))
+    sizes = [struct.unpack_from("<I", b, len(b) - 4)[0] for _, b, _, _ in rows]
+    err, status, raw = _run(bam, [r[1] for r in rows])
+    got = _slots(raw, sizes)
+    assert status.size == len(rows)
+    for k, (name, b, p, st) in enumerate(rows):
+        if p is not None:
+            assert status[k] == 0 and got[k] == p, name
+        else:
+            assert bam.INFLATE_STATUS[status[k]] == st, (name, bam.INFLATE_STATUS[status[k]])
+    assert {st for _, _, st in bad} == {"BAD_SYMBOL", "BAD_CODE_LENGTHS", "BAD_DISTANCE", "OUTPUT_OVERRUN"}
+    assert err is not None and "block 1 of the file, at byte %d," % len(rows[0][1]) in str(err) and bad[0][2] in str(err)
+
+
+# ------------------------------------------------------------------------------------------------ the record scan where a wrong guess succeeds
+DECOY = (777, 0x12345678, -77777, 0xBEEF | (0xAB << 16))     # refID, pos, tlen, flag | mapq << 16 of the fake records: nowhere else in the files
+
+
+def _raw_record(refid, pos, mapq, flag, tlen, tail=b""):
+    """a record of the 32 fixed bytes and `tail` (no read name, no CIGAR, no bases: to the scanner a record is its block_size word and its fixed part)"""
+    body = struct.pack("<iiBBHHHIiii", refid, pos, 0, mapq, 4680, 0, flag, 0, -1, -1, tlen) + tail
+    return struct.pack("<i", len(body)) + body
+
+
+def _fake(tail_bytes=8):
+    return _raw_record(DECOY[0], DECOY[1], DECOY[3] >> 16, DECOY[3] & 0xFFFF, DECOY[2], b"\x55" * tail_bytes)
+
+
+def _decoy_file(path, variant):
+    """a file with one record whose tail is a chain of fake records, and a BGZF block cut to begin at the first of them.  The walk from that
+    block's first byte (the guess) goes along the fakes and then (a) arrives at the true record's end inside the block and goes on along true
+    records, (b) meets a bad block_size word, (c) meets a block_size that reaches past the end of the file, (d) leaves the block exactly at the
+    next block's first byte, which is the true record's end"""
+    head, first = rck.bam_stream("@HD\tVN:1.0\n", REFS, _recs(20))
+    after, first2 = rck.bam_stream("@HD\tVN:1.0\n", REFS, _recs(60))
+    after = after[_offsets(after, first2)[20]:]              # records 20 .. 59 of the same kind
+    pad = b"\x01" * 10
+    tail = pad + b"".join(_fake(8 * (k % 3)) for k in range(5))
+    if variant == "b":
+        tail += struct.pack("<i", 7) + b"\x02" * 40
+    elif variant == "c":
+        tail += struct.pack("<i", 1 << 27) + b"\x02" * 40
+    rec = _raw_record(1, 5000, 33, 0x3, 150, tail)
+    decoy_at = len(head) + 36 + len(pad)                     # the first fake's block_size word
+    stream = head + rec + after
+    true_end = len(head) + len(rec)
+    if variant == "d":
+        sizes = [decoy_at, true_end - decoy_at, 700, len(stream)]
+    else:
+        sizes = [decoy_at, true_end - decoy_at + 700 + 13, 500, len(stream)]     # the block goes on through true records and ends inside one
+    rck.write_bgzf(path, stream, sizes)
+    # what the guess walks over, by the scanner's own rule: the fakes parse as a chain that starts at the block's first byte
+    got = struct.unpack_from("<iii", stream, decoy_at)
+    assert got[0] >= 32 and got[1:] == DECOY[:2]
+    return stream, first
+
+
+@pytest.mark.parametrize("variant", ["a", "b", "c", "d"])
+def test_scan_decoy_chain(bam, tmp_path, variant):
+    import numpy as np
+    p = str(tmp_path / "decoy.bam")
+    _decoy_file(p, variant)
+    want = bam.BamFile(p).records()
+    assert want[0].size == 61 and not any((w == np.asarray(v).astype(w.dtype)).any() for w, v in zip(want, DECOY))
+    for batch_bytes in (32 << 20, 1):
+        got = bam.DeviceBamFile(p, batch_bytes=batch_bytes).records()
+        assert _same(got, want), (variant, batch_bytes)
+        assert not any((g == np.asarray(v).astype(g.dtype)).any() for g, v in zip(got, DECOY))
+
+
+EMPTY_AT = (0, 1, 255, 256, 257)
+
+
+@pytest.mark.parametrize("straddle", [False, True])
+def test_scan_empty_blocks_mid_file(bam, tmp_path, straddle):
+    """empty data blocks, as a concatenated BGZF file has them, as the first, second, 256th, 257th and 258th data block and as the last one before
+    the end-of-file block; blocks cut at record boundaries, and at a fixed payload so that records straddle them"""
+    n = 300
+    stream, first = rck.bam_stream("@HD\tVN:1.0\n", REFS, _recs(n))
+    offs = _offsets(stream, first) + [len(stream)]
+    data = [50] * (-(-(len(stream) - first) // 50)) if straddle else [offs[k + 1] - offs[k] for k in range(n)]
+    for k in EMPTY_AT:
+        data.insert(k, 0)
+    assert len(data) > 258 and all(data[k] == 0 for k in EMPTY_AT) and sum(data) >= len(stream) - first
+    p = str(tmp_path / "empty.bam")
+    rck.write_bgzf(p, stream, [first] + data, eof=False)
+    with open(p, "ab") as f:
+        f.write(rck.bgzf_block(b"") + rck.EOF_BLOCK)
+    assert rck.parse_bam(p)["n_blocks"] == 1 + len(data) + 2 <= 600
+    want = bam.BamFile(p).records()
+    assert want[0].size == n
+    for batch_bytes in (32 << 20, 1):
+        assert _same(bam.DeviceBamFile(p, batch_bytes=batch_bytes).records(), want), (straddle, batch_bytes)
+
+
+@pytest.mark.parametrize("place", ["first", "middle", "last"])
+def test_scan_record_longer_than_a_block(bam, tmp_path, place):
+    """one record of 180 KB (l_seq = 120 000) among short ones: it spans four BGZF blocks of 60 000 bytes"""
+    recs = _recs(30)
+    at = {"first": 0, "middle": 15, "last": 30}[place]
+    recs.insert(at, (1, 424242, 44, 0x3, 99, 5, 1, 120000))
+    p = str(tmp_path / "long.bam")
+    stream, first = rck.write_bam(p, "@HD\tVN:1.0\n", REFS, recs, payload_sizes=60000)
+    offs = _offsets(stream, first) + [len(stream)]
+    assert offs[at + 1] - offs[at] > 65536 and offs[at + 1] // 60000 - offs[at] // 60000 >= 3
+    want = bam.BamFile(p).records()
+    assert want[0].size == 31 and want[1][at] == 424242
+    for batch_bytes in (32 << 20, 1):
+        assert _same(bam.DeviceBamFile(p, batch_bytes=batch_bytes).records(), want), (place, batch_bytes)
+
+
+def test_scan_densest_stream(bam, tmp_path):
+    """records of block_size 32 -- 36 bytes each, the shortest the scanner takes -- in more than 256 blocks of 4 096 bytes: the record arrays' room
+    (total / 36 + 1) is used to the last element but the header's share"""
+    import numpy as np
+    n = 30000
+    head, first = rck.bam_stream("@HD\tVN:1.0\n", REFS, [])
+    stream = head + b"".join(_raw_record(k % 2, 100 + 3 * k, k % 61, 0x3 if k % 3 else 0x11, 150 - (k % 5) * 60) for k in range(n))
+    p = str(tmp_path / "dense.bam")
+    rck.write_bgzf(p, stream, 4096)
+    assert 256 < rck.parse_bam(p)["n_blocks"] <= 600 and len(stream) == first + 36 * n
+    want = bam.BamFile(p).records()
+    assert want[0].size == n and np.array_equal(want[1], 100 + 3 * np.arange(n, dtype=np.int32))
+    for batch_bytes in (32 << 20, 1):
+        assert _same(bam.DeviceBamFile(p, batch_bytes=batch_bytes).records(), want), batch_bytes
