@@ -12,6 +12,8 @@ from .api import (Batch, Cohort, MultiDevice, DeviceArray, device_count, PinnedA
                   CALL_BOUNDS_DTYPE,
                   PowerMap, detection_power, region_runs, power_geometry, power_from_moments, POWER_DTYPE,
                   QuantileMap, normal_range, qbetabinom, qbetabinom_ab, quantile_geometry,
+                  runif53, rbetabinom, rbetabinom_ab, rbetabinom_ab_u, sim_geometry, planted_prob, SimulatedCounts, null_call_table,
+                  false_calls_per_sample, NULL_CALL_DTYPE,
                   call_copy_number, copy_number_from_profile, ratio_geometry, CALL_DTYPE, COPY_RATIO_GRID)
 
 __all__ = ["Batch", "Cohort", "MultiDevice", "DeviceArray", "device_count", "PinnedArray", "ExomeDepth", "Plan", "Posterior", "fit_transitions", "fit_prop_tumor", "mixture_geometry", "EdError", "chromosome_order", "cohort_select_reference_sets", "refcohort_last_path", "fit_betabin", "fit_betabin_bins",
@@ -22,4 +24,6 @@ __all__ = ["Batch", "Cohort", "MultiDevice", "DeviceArray", "device_count", "Pin
            "CALL_BOUNDS_DTYPE",
            "PowerMap", "detection_power", "region_runs", "power_geometry", "power_from_moments", "POWER_DTYPE",
            "QuantileMap", "normal_range", "qbetabinom", "qbetabinom_ab", "quantile_geometry",
+           "runif53", "rbetabinom", "rbetabinom_ab", "rbetabinom_ab_u", "sim_geometry", "planted_prob", "SimulatedCounts", "null_call_table",
+           "false_calls_per_sample", "NULL_CALL_DTYPE",
            "call_copy_number", "copy_number_from_profile", "ratio_geometry", "CALL_DTYPE", "COPY_RATIO_GRID"]

@@ -232,6 +232,12 @@ SYMBOLS = [
     ("ed_batch_copy_call_ratio_profile_dd", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _i64]),
     ("ed_batch_call_ratio_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("ed_ratio_geometry", C.c_int, [C.POINTER(_i32)]),
+    ("ed_runif53", C.c_int, [C.c_uint64, _vp, _vp, _vp, C.c_uint32, _i64, _vp]),
+    ("ed_rbetabinom_ab_u", C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    ("ed_plan_simulate", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_uint64, _i64, _vp, _vp, _vp]),
+    ("ed_plan_simulate_cells", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, C.c_uint64, _i64, C.c_uint32, _vp, _vp, _vp]),
+    ("ed_sim_stats", C.c_int, [_vp, _vp]),
+    ("ed_sim_geometry", C.c_int, [C.POINTER(_i32)]),
 ]
 
 

@@ -372,6 +372,17 @@ class Plan:
         power_map takes them; probs: 1 .. 16 probabilities inside (0, 1), strictly ascending."""
         return QuantileMap(self, test, ref, phi, expected, probs, layout, stream)
 
+    def simulate(self, test, ref, phi, expected, seed, replicate=0, sample0=0, layout=0, stream=None, plant=None):
+        """A cohort's counts redrawn under its own fitted normal state (include/exomedepth_amd.h: ed_plan_simulate): every cell keeps its
+        total n = test + ref, test* is the draw from BetaBinomial(n; phi_s, expected_s) at the uniform of the counter (exon, sample0 + s,
+        replicate, 0) under `seed`, ref* = n - test*.  test / ref: int32 counts, (n_exons, S) with layout 0 or (S, n_exons) with layout 1,
+        host arrays, DeviceArrays or torch device tensors; phi, expected: one value per sample (host).  Returns SimulatedCounts: the pair
+        (test*, ref*) of DeviceArrays in the input's layout -- they go straight into Batch.fit / Batch.run / Cohort.submit -- with .stats().
+        A seed reproduces a sample's draws alone or in any slab (pass the slab's first global sample index as sample0), in either layout.
+        plant = (rows, ratio): the cells of those rows are then redrawn at the proportion e c / (e c + 1 - e) of copy ratio c, on stream 1
+        (rows: records with sample, start_exon, end_exon, or (chrom, first, last) triples for every sample)."""
+        return _simulate(self, test, ref, phi, expected, seed, replicate, sample0, layout, stream, plant)
+
     def close(self):
         if self.handle:
             lib().ed_plan_destroy(self.handle)
@@ -2123,6 +2134,260 @@ def normal_range(chrom_off, start, end, test, ref, phi, expected, rows=None, pro
         plan.close()
 
 
+# ---------------------------------------------------------------------------------------------
+# draws from the fitted model: rbetabinom, null cohorts, and what a Bayes factor means on data without a CNV
+# ---------------------------------------------------------------------------------------------
+STREAM_NULL, STREAM_PLANTED = 0, 1
+NULL_CALL_DTYPE = np.dtype([("replicate", "<i4")] + CALL_DTYPE.descr + CALL_INFO_DTYPE.descr)
+
+
+def sim_geometry():
+    """{walk_tile, occupancy_cap, max_total, region_tile, chunk} of the draw kernels (ed_sim_geometry); chunk: the cells one walk serves"""
+    out = (C.c_int32 * 5)()
+    check(lib().ed_sim_geometry(out))
+    return dict(zip(("walk_tile", "occupancy_cap", "max_total", "region_tile", "chunk"), (int(v) for v in out)))
+
+
+def _u32(x, what):
+    a = np.atleast_1d(np.asarray(x))
+    if a.dtype.kind not in "iu":
+        raise ValueError("%s must be whole numbers" % what)
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 0xffffffff):
+        raise ValueError("%s must lie in 0 .. 2^32 - 1" % what)
+    return a.astype(np.uint32).ravel()
+
+
+def _seed64(seed):
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must lie in 0 .. 2^64 - 1")
+    return seed
+
+
+def runif53(seed, exon, sample, replicate, stream=0):
+    """The uniforms behind the draws (include/exomedepth_amd.h: ed_runif53): Philox4x32-10 under the key of the 64-bit `seed` at the
+    counters (exon, sample, replicate, stream), recycled to the longest; u = (2 k + 1) 2^-53 of 52 output bits: never 0, never 1.
+    A float64 array."""
+    args = [_u32(exon, "exon"), _u32(sample, "sample"), _u32(replicate, "replicate")]
+    n = 0 if any(a.size == 0 for a in args) else max(a.size for a in args)
+    args = [np.ascontiguousarray(np.resize(a, n)) for a in args]
+    out = np.zeros(n)
+    check(lib().ed_runif53(_seed64(seed), *[_ptr(a) if n else None for a in args], int(_u32(stream, "stream")[0]), n, _ptr(out) if n else None))
+    return out
+
+
+def rbetabinom_ab_u(u, size, shape1, shape2):
+    """The draw from BetaBinomial(size, shape1, shape2) at a given uniform, element by element (ed_rbetabinom_ab_u): the smallest x in
+    0 .. size whose distribution function exceeds u -- qbetabinom_ab's cut --, size where nothing crosses.  Recycled to the longest as
+    qbetabinom_ab recycles; an int32 array.  -1 where u is outside [0, 1), a shape is not positive and finite or size is not a whole
+    number in 0 .. max_total (sim_geometry)."""
+    args = [_f64(np.atleast_1d(x)).ravel() for x in (u, size, shape1, shape2)]
+    n = 0 if any(a.size == 0 for a in args) else max(a.size for a in args)
+    args = [np.ascontiguousarray(np.resize(a, n)) for a in args]
+    out = np.zeros(n, dtype=np.int32)
+    check(lib().ed_rbetabinom_ab_u(*[_ptr(a) if n else None for a in args], n, _ptr(out) if n else None))
+    return out
+
+
+def rbetabinom_ab(size, shape1, shape2, seed, index=None, replicate=0):
+    """Draws from BetaBinomial(size, shape1, shape2), recycled to the longest: element i is rbetabinom_ab_u at the uniform of the counter
+    (index[i] -- i when index is None --, 0, replicate, 0) under `seed`.  The same (seed, index, replicate) gives the same draw in any
+    call, whatever else the call holds."""
+    args = [_f64(np.atleast_1d(x)).ravel() for x in (size, shape1, shape2)]
+    idx = None if index is None else _u32(index, "index")
+    sizes = [a.size for a in args] + ([idx.size] if idx is not None else [])
+    n = 0 if any(k == 0 for k in sizes) else max(sizes)
+    idx = np.arange(n, dtype=np.uint32) if idx is None else np.resize(idx, n)
+    u = runif53(seed, idx, 0, replicate, STREAM_NULL) if n else np.zeros(0)
+    return rbetabinom_ab_u(u, *[np.resize(a, n) for a in args])
+
+
+def rbetabinom(size, phi, prob, seed, index=None, replicate=0):
+    """rbetabinom_ab at shape1 = prob (1 - phi) / phi, shape2 = (1 - prob)(1 - phi) / phi, formed as qbetabinom forms them"""
+    phi, prob = _f64(np.atleast_1d(phi)).ravel(), _f64(np.atleast_1d(prob)).ravel()
+    n = 0 if not (phi.size and prob.size) else max(phi.size, prob.size)
+    phi, prob = np.resize(phi, n), np.resize(prob, n)
+    with np.errstate(all="ignore"):
+        a, b = prob * (1. - phi) / phi, (1. - prob) * (1. - phi) / phi
+    return rbetabinom_ab(size, a, b, seed, index, replicate)
+
+
+def planted_prob(expected, ratio):
+    """the proportion of test reads of a cell at copy ratio `ratio`: e c / (e c + 1 - e), the caller's own odds rule"""
+    e, c = np.asarray(expected, dtype=np.float64), np.asarray(ratio, dtype=np.float64)
+    return e * c / (e * c + 1 - e)
+
+
+def _plant_cells(plant, n_exons, S, layout, phi, expected):
+    """plant = (rows, ratio) -> (exon, sample, a, b) of every planted cell, a cell named twice taken once (its last row counts).  rows:
+    records with sample, start_exon, end_exon (a call table), or (chrom, first, last) triples standing for every sample; ratio: a
+    scalar or one per row, > 0 and finite."""
+    rows, ratio = plant
+    a = np.asarray(rows)
+    per_sample = bool(a.dtype.names and "sample" in a.dtype.names)
+    rows = _ratio_rows(rows) if per_sample else _region_rows(rows)
+    ratio = np.asarray(ratio, dtype=np.float64)
+    if ratio.ndim == 0:
+        ratio = np.full(rows.size, float(ratio))
+    if ratio.shape != (rows.size,):
+        raise ValueError("plant: ratio must be a scalar or one value per row")
+    if not np.all(np.isfinite(ratio) & (ratio > 0)):
+        raise ValueError("plant: every ratio must be finite and > 0")
+    first, last = rows["start_exon"].astype(np.int64), rows["end_exon"].astype(np.int64)
+    if rows.size and (first.min() < 0 or last.max() >= n_exons or np.any(first > last)):
+        raise ValueError("plant: a row does not lie inside the plan's exons")
+    if per_sample and rows.size and (rows["sample"].min() < 0 or rows["sample"].max() >= S):
+        raise ValueError("plant: a row names a sample outside the counts")
+    cells = {}
+    for r in range(rows.size):
+        for s in ([int(rows["sample"][r])] if per_sample else range(S)):
+            for e in range(int(first[r]), int(last[r]) + 1):
+                cells[(e, s)] = ratio[r]
+    keys = sorted(cells)
+    ce = np.array([k[0] for k in keys], dtype=np.int32)
+    cs = np.array([k[1] for k in keys], dtype=np.int32)
+    c = np.array([cells[k] for k in keys], dtype=np.float64)
+    ph, pr = phi[cs], planted_prob(expected[cs], c)
+    with np.errstate(all="ignore"):
+        return ce, cs, pr * (1. - ph) / ph, (1. - pr) * (1. - ph) / ph
+
+
+class SimulatedCounts(tuple):
+    """(test*, ref*) of Plan.simulate: two DeviceArrays of int32 counts in the input's layout, and .stats() of the draw"""
+
+    def __new__(cls, test, ref, stats):
+        self = super().__new__(cls, (test, ref))
+        self._stats = stats
+        return self
+
+    def stats(self):
+        """n_jobs (occupied (sample, total) pairs), tiles_walked, tiles_full (one full walk per 64 cells of the same jobs), cells_drawn,
+        cells_skipped (kept as they were: a total outside 0 .. max_total, or a sample whose shapes are outside the model),
+        n_bad_samples, n_planted; occupancy_ms, grouping_ms, walk_ms, host-timed between waits"""
+        return dict(self._stats)
+
+    def free(self):
+        for d in self:
+            d.free()
+
+
+def _simulate(plan, test, ref, phi, expected, seed, replicate=0, sample0=0, layout=0, stream=None, plant=None):
+    phi, expected = _f64(np.atleast_1d(phi)).ravel(), _f64(np.atleast_1d(expected)).ravel()
+    S = int(phi.size)
+    if expected.size != S:
+        raise ValueError("phi and expected must have one value per sample")
+    E = plan.n_exons
+    for x in (test, ref):
+        _check_counts_shape(x, E, S, layout)
+    cells = _plant_cells(plant, E, S, layout, phi, expected) if plant is not None else None
+    shape = (S, E) if layout else (E, S)
+    out = [DeviceArray(nbytes=max(E * S, 1) * 4) for _ in range(2)]
+    try:
+        for d in out:
+            d.host_dtype, d.shape = np.dtype(np.int32), shape
+        with _staged() as keep:
+            pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
+            st = C.c_void_p(stream or 0)
+            check(lib().ed_plan_simulate(plan.handle, pt, pr, _ptr(phi), _ptr(expected), S, int(sample0), int(layout), _seed64(seed),
+                                         int(replicate), out[0].ptr, out[1].ptr, st))
+            cnt, ms = (C.c_int64 * 6)(), (C.c_double * 3)()
+            check(lib().ed_sim_stats(cnt, ms))
+            stats = dict(zip(("n_jobs", "tiles_walked", "tiles_full", "cells_drawn", "cells_skipped", "n_bad_samples"), (int(v) for v in cnt)))
+            stats.update(zip(("occupancy_ms", "grouping_ms", "walk_ms"), (float(v) for v in ms)))
+            stats["n_planted"] = 0
+            if cells is not None and cells[0].size:
+                ce, cs, a, b = cells
+                check(lib().ed_plan_simulate_cells(plan.handle, pt, pr, _ptr(ce), _ptr(cs), _ptr(a), _ptr(b), int(ce.size), S, int(sample0),
+                                                   int(layout), _seed64(seed), int(replicate), STREAM_PLANTED, out[0].ptr, out[1].ptr, st))
+                stats["n_planted"] = int(ce.size)
+    except Exception:
+        for d in out:
+            d.free()
+        raise
+    return SimulatedCounts(out[0], out[1], stats)
+
+
+def null_call_table(chrom_off, start, end, test, ref, phi, expected, replicates, seed, refit=True, transition_probability=1e-4,
+                    expected_CNV_length=50000, plant=None, device=0):
+    """What the unchanged pipeline calls on data drawn from the fitted model itself.  Per replicate (replicates: a count, or the
+    replicate numbers): draw the cohort (Plan.simulate; with plant = (rows, ratio) the planted cells on top), then -- refit=True -- fit
+    phi and expected on the draw as a real run would (Batch.fit) and run (Batch.run), or run at the given parameters.  test / ref:
+    (n_exons, S) int32 counts.  Returns a dict: calls, a NULL_CALL_DTYPE array -- every replicate's call table with call_info's columns
+    (BF among them) under a `replicate` column --; replicates (R,); phi, expected (R, S), the parameters each replicate ran at;
+    n_samples; n_null_samples = R x S, what false_calls_per_sample divides by; stats, each draw's SimulatedCounts.stats()."""
+    reps = list(range(int(replicates))) if np.ndim(replicates) == 0 else [int(r) for r in replicates]
+    phi, expected = _f64(np.atleast_1d(phi)).ravel(), _f64(np.atleast_1d(expected)).ravel()
+    S = int(phi.size)
+    plan = Plan(chrom_off, start, end, transition_probability, expected_CNV_length, device)
+    batch = None
+    tables, phis, exps, stats = [], [], [], []
+    try:
+        batch = Batch(plan, S)
+        with _staged() as keep:
+            for x in (test, ref):
+                _check_counts_shape(x, plan.n_exons, S, 0)
+            pt, pr = _RawDevice(_device_pointer(test, np.int32, keep).value), _RawDevice(_device_pointer(ref, np.int32, keep).value)
+            for r in reps:
+                sim = plan.simulate(pt, pr, phi, expected, seed, replicate=r, plant=plant)
+                try:
+                    if refit:
+                        dp, de = DeviceArray(nbytes=S * 8), DeviceArray(nbytes=S * 8)
+                        keep.extend([dp, de])
+                        batch.fit(sim[0], sim[1], dp, de)
+                        batch.run(sim[0], sim[1], dp, de)
+                        calls, info = batch.calls(), batch.call_info()
+                        phis.append(dp.to_host(np.float64, (S,)))
+                        exps.append(de.to_host(np.float64, (S,)))
+                    else:
+                        batch.run(sim[0], sim[1], phi, expected)
+                        calls, info = batch.calls(), batch.call_info()
+                        phis.append(phi.copy())
+                        exps.append(expected.copy())
+                finally:
+                    sim.free()
+                stats.append(sim.stats())
+                t = np.zeros(calls.size, dtype=NULL_CALL_DTYPE)
+                t["replicate"] = r
+                for k in CALL_DTYPE.names:
+                    t[k] = calls[k]
+                for k in CALL_INFO_DTYPE.names:
+                    t[k] = info[k]
+                tables.append(t)
+    finally:
+        if batch is not None:
+            batch.close()
+        plan.close()
+    R = len(reps)
+    return {"calls": np.concatenate(tables) if tables else np.zeros(0, dtype=NULL_CALL_DTYPE), "replicates": np.array(reps, dtype=np.int64),
+            "phi": np.array(phis).reshape(R, S), "expected": np.array(exps).reshape(R, S), "n_samples": S, "n_null_samples": R * S,
+            "stats": stats}
+
+
+def false_calls_per_sample(bf, null_bf, n_null_samples, kind=None, null_kind=None):
+    """For every real call: #{null calls of its type with BF >= its BF} / n_null_samples -- the number of calls at least this strong
+    that the pipeline is expected to make in one exome with no CNV in it.  bf: the real calls' Bayes factors; null_bf: those of a null
+    table (null_call_table's calls["BF"]); n_null_samples: the samples the null table was drawn for (replicates x samples).  kind /
+    null_kind: the calls' types (1 deletion, 2 duplication, or any labels); both or neither; without them every null call counts.  On the
+    host: a sort and a binary search per type.  NaN where a real BF is NaN; a null BF that is NaN counts nowhere."""
+    bf, null_bf = np.asarray(bf, dtype=np.float64).ravel(), np.asarray(null_bf, dtype=np.float64).ravel()
+    if not n_null_samples > 0:
+        raise ValueError("n_null_samples must be positive")
+    if (kind is None) != (null_kind is None):
+        raise ValueError("kind and null_kind go together")
+    if kind is None:
+        kind, null_kind = np.zeros(bf.size, dtype=np.int64), np.zeros(null_bf.size, dtype=np.int64)
+    kind, null_kind = np.asarray(kind).ravel(), np.asarray(null_kind).ravel()
+    if kind.size != bf.size or null_kind.size != null_bf.size:
+        raise ValueError("one type per call")
+    out = np.zeros(bf.size)
+    for t in np.unique(kind):
+        mine = kind == t
+        pool = np.sort(null_bf[(null_kind == t) & ~np.isnan(null_bf)])
+        out[mine] = (pool.size - np.searchsorted(pool, bf[mine], "left")) / float(n_null_samples)
+    out[np.isnan(bf)] = np.nan
+    return out
+
+
 def chromosome_order(chromosome, start, end):
     """Return (order, chrom_levels, chrom_codes_sorted, chrom_off).  Levels are '1'..'22' first (those
     present), then the other names in first-seen order; exons are ordered by (level, midpoint) with
@@ -2442,6 +2707,24 @@ class ExomeDepth:
             out["my_max_norm_prop"] = out["my_max_norm"] / out["total_counts"]
             out["outside"] = (out["ratio"] > out["my_max_norm_prop"] / expected).astype(np.int8) - (out["ratio"] < out["my_min_norm_prop"] / expected).astype(np.int8)
         return out
+
+    def null_calls(self, chromosome, start, end, replicates=100, seed=0, refit=True, transition_probability=1e-4, expected_CNV_length=50000.0,
+                   plant=None):
+        """What CallCNVs calls on draws from this sample's own fitted model (null_call_table on one sample; not in the reference): the
+        dict null_call_table returns, its calls' exon indices in CallCNVs' order.  With the object's own calls,
+        false_calls_per_sample([c["BF"] ...], out["calls"]["BF"], out["n_null_samples"], kinds, out["calls"]["type"]) says how many calls
+        that strong an exome without a CNV is expected to give.  Nothing of the object is changed."""
+        n = self.test.size
+        if not (len(start) == len(chromosome) == len(end) == n):
+            raise ValueError("The annotation vectors must have the same length as the data in the ExomeDepth x")
+        if self.phi.size == 0:
+            raise ValueError("the object has no fitted phi / expected (too few bins with reads)")
+        if not (np.all(self.phi == self.phi[0]) and np.all(self.expected == self.expected[0])):
+            raise NotImplementedError("null_calls with a per-exon phi or expected (phi.bins > 1, covariates) is not implemented")
+        order, _, _, chrom_off = chromosome_order(chromosome, start, end)
+        return null_call_table(chrom_off, np.asarray(start)[order], np.asarray(end)[order], _as_r_integer(self.test[order]).reshape(n, 1),
+                               _as_r_integer(self.reference[order]).reshape(n, 1), self.phi[:1], self.expected[:1], replicates, seed, refit=refit,
+                               transition_probability=transition_probability, expected_CNV_length=expected_CNV_length, plant=plant)
 
     def AnnotateExtra(self, reference_annotation, min_overlap=0.5, column_name=None):
         """reference R/annotate_extra.R:41-73: adds `column_name` to every row of CNV_calls -- the `names` of the annotation's intervals the

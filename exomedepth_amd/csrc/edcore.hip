@@ -57,6 +57,7 @@
 #include "ed_mix_plan.hpp"
 #include "ed_power_plan.hpp"
 #include "ed_quant_plan.hpp"
+#include "ed_philox.hpp"
 #include "ed_ratio_plan.hpp"
 #include "ed_rows.hpp"
 
@@ -3005,3 +3006,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edratio.inc"       // (the call decoration's dd_add) and again
 #include "edquant.inc"       // (edpower.inc's occupancy) and again
 #include "edinflate.inc"     // (nothing of the others) last, for the same reason
+#include "edsim.inc"         // (edpower.inc's occupancy, edannot.inc's scan) and again

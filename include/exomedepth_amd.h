@@ -461,6 +461,45 @@ int ed_quant_stats(const ed_quant* map, int64_t counts[11], double ms[4]);
 int ed_quant_geometry(int32_t out[5]);
 int ed_qbetabinom_ab(const double* p, const double* size, const double* shape1, const double* shape2, int64_t n, double* out);
 
+/* ---- draws from the fitted model: rbetabinom, and a cohort's counts redrawn under its own fitted normal state ----
+ * For a size n, shapes (a, b) and a uniform u, with C the running sum of the beta-binomial masses as the quantile map forms it:
+ *   the draw = the smallest x in 0 .. n with C(x) > u;  n when nothing crosses (u within rounding of 1);  0 for n = 0
+ * -- inversion of the distribution function, the quantile map's cut at p = u.
+ * The uniform is counter-based (csrc/ed_philox.hpp): Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (exon, sample,
+ * replicate, stream) with exon the exon's index in the plan, sample the GLOBAL sample index (sample0 + the index in the slab), stream 0 for
+ * the null draw and 1 for planted cells.  From the output words w0 .. w3: k = (w0 >> 12) 2^32 + w1, u = (2 k + 1) 2^-53: exact, never 0,
+ * never 1.  A seed therefore reproduces a cell's draw whatever the number of samples in the call, their order, the layout or sample0's split.
+ * The bits of a draw depend on (n, a, b, u) alone.
+ * ed_runif53: HOST uint32 arrays [n] of counters to HOST double [n], made by the device code the draws use.
+ * ed_rbetabinom_ab_u: the draw element by element over HOST arrays of length n, the uniform given: the cohort draw's walk, a wavefront per
+ *   element.  -1: u outside [0, 1), shapes that are not positive and finite, a size that is not a whole number in 0 .. the largest total walked.
+ * ed_plan_simulate: test / ref, test_out / ref_out: DEVICE int32 counts of n_samples samples of the plan's exons in `layout` (0: [E][S],
+ *   1: [S][E]); phi, expected: HOST double [n_samples]; sample s has a = expected (1 - phi) / phi, b = (1 - expected)(1 - phi) / phi in
+ *   qbetabinom's operation order.  Every cell: n = test + ref, test_out = the draw at u(seed, exon, sample0 + s, replicate, 0), ref_out =
+ *   n - test_out.  A cell whose total the occupancy map skips (a sum below 0 or above ed_sim_geometry's largest) and every cell of a sample
+ *   whose shapes are not positive and finite keep their input counts and are tallied.  One wavefront per occupied (sample, total) serves
+ *   all cells of that total from one walk.  Complete on return (it waits for `stream`).
+ *   ED_ERR_INVALID before anything is enqueued: a NULL pointer, a layout other than 0 / 1, n_samples outside 1 .. 2^20, replicate < 0,
+ *   sample0 < 0, outputs that overlap the inputs or each other.
+ * ed_plan_simulate_cells: listed cells of the same counts redrawn under shapes of their own -- cell_exon, cell_sample (index in the slab), a,
+ *   b: HOST arrays [n_cells] -- at u(seed, exon, sample0 + sample, replicate, stream_id); the total is read from test / ref, the draw
+ *   overwrites the cell in test_out / ref_out.  A cell whose total is not walked or whose shapes are outside the model is left as it is.
+ *   The same refusals, and a cell outside the counts.
+ * ed_sim_stats: of the calling thread's last ed_plan_simulate: counts = {jobs, tiles walked, tiles that one full walk per 64 cells of the
+ *   same jobs takes, cells drawn, cells skipped, samples outside the model}; ms (may be NULL) = {occupancy, grouping, walk}.
+ * ed_sim_geometry: out = ed_power_geometry's four, then the uniforms one walk holds (a job with more cells takes further walks). */
+int ed_runif53(uint64_t seed, const uint32_t* exon, const uint32_t* sample, const uint32_t* replicate, uint32_t stream_id, int64_t n,
+               double* u_out);
+int ed_rbetabinom_ab_u(const double* u, const double* size, const double* a, const double* b, int64_t n, int32_t* x_out);
+int ed_plan_simulate(const ed_plan* plan, const int32_t* test, const int32_t* ref, const double* phi, const double* expected,
+                     int64_t n_samples, int64_t sample0, int layout, uint64_t seed, int64_t replicate, int32_t* test_out, int32_t* ref_out,
+                     void* stream);
+int ed_plan_simulate_cells(const ed_plan* plan, const int32_t* test, const int32_t* ref, const int32_t* cell_exon, const int32_t* cell_sample,
+                           const double* a, const double* b, int64_t n_cells, int64_t n_samples, int64_t sample0, int layout, uint64_t seed,
+                           int64_t replicate, uint32_t stream_id, int32_t* test_out, int32_t* ref_out, void* stream);
+int ed_sim_stats(int64_t counts[6], double ms[3]);
+int ed_sim_geometry(int32_t out[5]);
+
 /* ---- the copy-ratio profile: how many copies is a call? ----
  * The HMM's states stand for the copy ratios 0.5, 1 and 1.5; the beta-binomial emission is defined for any.  For a row (sample s, exons
  * start_exon .. end_exon, global indices as in ed_call) and a DOSE mu, -2 < mu <= 2 -- the copy ratio is r = 1 + mu / 2 --
