@@ -1839,32 +1839,87 @@ def _region_rows(rows):
     return out
 
 
-class PowerMap:
-    """Device-resident detection-power map of Plan.power_map: per sample the table of (total, mean_del, var_del, mean_dup, var_dup) of
-    its occupied totals, and per (sample, exon) the table slot of the exon's total.  mean_T is the expected contribution of an exon to a
-    call's BF column when the exon truly is in state T, var_T its variance (include/exomedepth_amd.h)."""
+_MAP_COUNTERS = ("n_samples", "n_exons", "n_jobs", "max_jobs", "n_skipped", "n_bad_samples", "largest_total", "map_words")
 
-    def __init__(self, plan, test, ref, phi, expected, mixture=1.0, layout=0, stream=None):
+
+class _TotalsMap:
+    """What the device-resident maps indexed by a cell's total share (csrc/edtotals.inc): a handle of the entries ed_<_ENTRY>_*, the
+    samples' parameters, the staging of the counts, a sample's table, the common counters."""
+    _ENTRY = None       # "power", "quant"
+
+    def __init__(self, plan, phi, expected, stream):
         self.plan, self.stream = plan, stream
-        phi, expected = _f64(np.atleast_1d(phi)), _f64(np.atleast_1d(expected))
-        S = _n_samples_of(phi)
-        if expected.size != S:
+        self._phi, self._expected = _f64(np.atleast_1d(phi)), _f64(np.atleast_1d(expected))
+        self.n_samples = _n_samples_of(self._phi)
+        if self._expected.size != self.n_samples:
             raise ValueError("phi and expected must have one value per sample")
-        self.n_samples = S
-        mix = _per_sample_mixture(mixture, S)
+        self.handle = C.c_void_p()
+
+    def _counts(self, test, ref, layout, keep):
+        """(test pointer, ref pointer, on the device?) inside `with _staged() as keep`"""
         on_dev = _is_device(test) and _is_device(ref)
         if not on_dev and (_is_device(test) or _is_device(ref)):
             raise ValueError("test and ref must both be device arrays or both be host arrays")
-        self.handle = C.c_void_p()
+        if on_dev:
+            return _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep), 1
+        test, ref = _i32(test), _i32(ref)
+        for x in (test, ref):
+            _check_counts_shape(x, self.plan.n_exons, self.n_samples, layout)
+        keep.extend((test, ref))       # (the converted copies live as long as the call)
+        return _ptr(test), _ptr(ref), 0
+
+    @staticmethod
+    def _live_rows(rows):
+        """(rows as call-shaped records, the mask of the (chrom, -1, -1) rows, the others contiguous)"""
+        rows = _region_rows(rows)
+        none = (rows["start_exon"] == -1) & (rows["end_exon"] == -1)
+        return rows, none, np.ascontiguousarray(rows[~none])
+
+    def _entry(self, what):
+        return getattr(lib(), "ed_%s_%s" % (self._ENTRY, what))
+
+    def _table(self, sample, *channels):
+        """(totals [k], values [*channels][max(k, 1)], k) of the sample: one call for k, one for the arrays"""
+        n = C.c_int64(0)
+        check(self._entry("copy_table")(self.handle, int(sample), None, None, 0, C.byref(n)))
+        k = int(n.value)
+        totals, values = np.zeros(k, dtype=np.int32), np.zeros(channels + (max(k, 1),))
+        if k:
+            check(self._entry("copy_table")(self.handle, int(sample), _ptr(totals), _ptr(values), k, C.byref(n)))
+        return totals, values, k
+
+    def _stats(self, *more):
+        cnt, ms = (C.c_int64 * (8 + len(more)))(), (C.c_double * 4)()
+        check(self._entry("stats")(self.handle, cnt, ms))
+        out = dict(zip(_MAP_COUNTERS + more, (int(v) for v in cnt)))
+        out.update(zip(("occupancy_ms", "walk_ms", "regions_ms", "exons_ms"), (float(v) for v in ms)))
+        return out
+
+    def free(self):
+        if self.handle:
+            self._entry("free")(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PowerMap(_TotalsMap):
+    """Device-resident detection-power map of Plan.power_map: per sample the table of (total, mean_del, var_del, mean_dup, var_dup) of
+    its occupied totals, and per (sample, exon) the table slot of the exon's total.  mean_T is the expected contribution of an exon to a
+    call's BF column when the exon truly is in state T, var_T its variance (include/exomedepth_amd.h)."""
+    _ENTRY = "power"
+
+    def __init__(self, plan, test, ref, phi, expected, mixture=1.0, layout=0, stream=None):
+        super().__init__(plan, phi, expected, stream)
+        S = self.n_samples
+        mix = _per_sample_mixture(mixture, S)
         with _staged() as keep:
-            if on_dev:
-                pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
-            else:
-                test, ref = _i32(test), _i32(ref)
-                for x in (test, ref):
-                    _check_counts_shape(x, plan.n_exons, S, layout)
-                pt, pr = _ptr(test), _ptr(ref)
-            check(lib().ed_plan_power_map(C.byref(self.handle), plan.handle, pt, pr, int(on_dev), int(layout), S, _ptr(phi), _ptr(expected),
+            pt, pr, on_dev = self._counts(test, ref, layout, keep)
+            check(lib().ed_plan_power_map(C.byref(self.handle), plan.handle, pt, pr, on_dev, int(layout), S, _ptr(self._phi), _ptr(self._expected),
                                           _ptr(mix) if mix is not None else None, 1.0 if mix is not None else float(mixture),
                                           C.c_void_p(stream or 0)))
 
@@ -1875,11 +1930,8 @@ class PowerMap:
         mean_T / var_T are the sums over the run's exons, n_empty counts its exons without reads, price is the evidence at which
         Viterbi prefers exactly this segment to all normal; power_T = power_from_moments(mean_T, var_T, threshold) with threshold =
         price unless given (a scalar or one value per region)."""
-        rows = _region_rows(rows)
-        R, S = rows.size, self.n_samples
-        none = (rows["start_exon"] == -1) & (rows["end_exon"] == -1)
-        live = np.ascontiguousarray(rows[~none])
-        n = int(live.size)
+        rows, none, live = self._live_rows(rows)
+        R, S, n = rows.size, self.n_samples, int(live.size)
         sums, empty = np.zeros((4, n, S)), np.zeros((n, S), dtype=np.int32)
         price, nex = np.zeros(n), np.zeros(n, dtype=np.int32)
         check(lib().ed_power_regions(self.handle, _ptr(live), n, _ptr(sums), _ptr(empty), _ptr(price), _ptr(nex), C.c_void_p(self.stream or 0)))
@@ -1905,12 +1957,7 @@ class PowerMap:
 
     def table(self, sample):
         """the sample's table: dict of totals (ascending, int32) and mean_del, var_del, mean_dup, var_dup"""
-        n = C.c_int64(0)
-        check(lib().ed_power_copy_table(self.handle, int(sample), None, None, 0, C.byref(n)))
-        k = int(n.value)
-        totals, values = np.zeros(k, dtype=np.int32), np.zeros((4, max(k, 1)))
-        if k:
-            check(lib().ed_power_copy_table(self.handle, int(sample), _ptr(totals), _ptr(values), k, C.byref(n)))
+        totals, values, k = self._table(sample, 4)
         return {"totals": totals, "mean_del": values[0, :k].copy(), "var_del": values[1, :k].copy(), "mean_dup": values[2, :k].copy(),
                 "var_dup": values[3, :k].copy()}
 
@@ -1918,22 +1965,7 @@ class PowerMap:
         """n_samples, n_exons, n_jobs (occupied totals over all samples), max_jobs (of one sample), n_skipped (cells whose total is above
         the largest one walked), n_bad_samples (parameters outside the model), largest_total, map_words; occupancy_ms, walk_ms,
         regions_ms, exons_ms (the last call of each), host-timed between waits"""
-        cnt, ms = (C.c_int64 * 8)(), (C.c_double * 4)()
-        check(lib().ed_power_stats(self.handle, cnt, ms))
-        out = dict(zip(("n_samples", "n_exons", "n_jobs", "max_jobs", "n_skipped", "n_bad_samples", "largest_total", "map_words"), (int(v) for v in cnt)))
-        out.update(zip(("occupancy_ms", "walk_ms", "regions_ms", "exons_ms"), (float(v) for v in ms)))
-        return out
-
-    def free(self):
-        if self.handle:
-            lib().ed_power_free(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return self._stats()
 
 
 def region_runs(chromosome, start, end, regions):
@@ -2029,33 +2061,20 @@ def qbetabinom(p, size, phi, prob):
     return qbetabinom_ab(p, size, a, b)
 
 
-class QuantileMap:
+class QuantileMap(_TotalsMap):
     """Device-resident quantile map of Plan.quantile_map: per sample the table of (total, q_k, below_k) of its occupied totals at the K
     requested probabilities, per (sample, exon) the table slot of the exon's total, and the test counts.  q_k = qbetabinom(p_k, total,
     phi, expected) under the sample's fitted normal state, below_k = the mass strictly below its cut (include/exomedepth_amd.h)."""
+    _ENTRY = "quant"
 
     def __init__(self, plan, test, ref, phi, expected, probs=(0.025, 0.975), layout=0, stream=None):
-        self.plan, self.stream = plan, stream
-        phi, expected = _f64(np.atleast_1d(phi)), _f64(np.atleast_1d(expected))
-        S = _n_samples_of(phi)
-        if expected.size != S:
-            raise ValueError("phi and expected must have one value per sample")
-        self.n_samples = S
+        super().__init__(plan, phi, expected, stream)
         self.probs = _f64(np.atleast_1d(probs)).ravel()
-        on_dev = _is_device(test) and _is_device(ref)
-        if not on_dev and (_is_device(test) or _is_device(ref)):
-            raise ValueError("test and ref must both be device arrays or both be host arrays")
-        self.handle = C.c_void_p()
         with _staged() as keep:
-            if on_dev:
-                pt, pr = _device_pointer(test, np.int32, keep), _device_pointer(ref, np.int32, keep)
-            else:
-                test, ref = _i32(test), _i32(ref)
-                for x in (test, ref):
-                    _check_counts_shape(x, plan.n_exons, S, layout)
-                pt, pr = _ptr(test), _ptr(ref)
-            check(lib().ed_plan_quantile_map(C.byref(self.handle), plan.handle, pt, pr, int(on_dev), int(layout), _ptr(phi), _ptr(expected),
-                                             _ptr(self.probs) if self.probs.size else None, int(self.probs.size), S, C.c_void_p(stream or 0)))
+            pt, pr, on_dev = self._counts(test, ref, layout, keep)
+            check(lib().ed_plan_quantile_map(C.byref(self.handle), plan.handle, pt, pr, on_dev, int(layout), _ptr(self._phi), _ptr(self._expected),
+                                             _ptr(self.probs) if self.probs.size else None, int(self.probs.size), self.n_samples,
+                                             C.c_void_p(stream or 0)))
 
     def regions(self, rows):
         """Per (region, sample), a dict of observed (n_regions, n_samples, K + 1) int32: the run's exons per bin, the bin of an exon being
@@ -2064,11 +2083,8 @@ class QuantileMap:
         read NaN and are in no bin; chi2 (n_regions, n_samples): sum over the bins with expected > 0 of (observed - expected)^2 /
         expected, on the host -- with a chromosome or the whole exome as the region, the sample's calibration statistic.  rows as
         PowerMap.regions takes them; a row of (chrom, -1, -1) is a region with no exon inside: zeros."""
-        rows = _region_rows(rows)
-        R, S, KB = rows.size, self.n_samples, self.probs.size + 1
-        none = (rows["start_exon"] == -1) & (rows["end_exon"] == -1)
-        live = np.ascontiguousarray(rows[~none])
-        n = int(live.size)
+        rows, none, live = self._live_rows(rows)
+        R, S, KB, n = rows.size, self.n_samples, self.probs.size + 1, int(live.size)
         obs, exp, empty = np.zeros((n, S, KB), dtype=np.int32), np.zeros((n, S, KB)), np.zeros((n, S), dtype=np.int32)
         check(lib().ed_quant_regions(self.handle, _ptr(live), n, _ptr(obs), _ptr(exp), _ptr(empty), C.c_void_p(self.stream or 0)))
         out = {"observed": np.zeros((R, S, KB), dtype=np.int32), "expected": np.zeros((R, S, KB)), "n_empty": np.zeros((R, S), dtype=np.int32)}
@@ -2088,34 +2104,13 @@ class QuantileMap:
 
     def table(self, sample):
         """the sample's table: dict of totals (ascending, int32), q (K, n_totals) and below (K, n_totals)"""
-        n = C.c_int64(0)
-        check(lib().ed_quant_copy_table(self.handle, int(sample), None, None, 0, C.byref(n)))
-        k, K = int(n.value), self.probs.size
-        totals, values = np.zeros(k, dtype=np.int32), np.zeros((2, K, max(k, 1)))
-        if k:
-            check(lib().ed_quant_copy_table(self.handle, int(sample), _ptr(totals), _ptr(values), k, C.byref(n)))
+        totals, values, k = self._table(sample, 2, self.probs.size)
         return {"totals": totals, "q": values[0, :, :k].copy(), "below": values[1, :, :k].copy()}
 
     def stats(self):
         """PowerMap.stats' counters (n_samples .. map_words), n_probs, tiles_walked, tiles_full (what full walks of the same jobs take), and its
         four times"""
-        cnt, ms = (C.c_int64 * 11)(), (C.c_double * 4)()
-        check(lib().ed_quant_stats(self.handle, cnt, ms))
-        out = dict(zip(("n_samples", "n_exons", "n_jobs", "max_jobs", "n_skipped", "n_bad_samples", "largest_total", "map_words", "n_probs",
-                        "tiles_walked", "tiles_full"), (int(v) for v in cnt)))
-        out.update(zip(("occupancy_ms", "walk_ms", "regions_ms", "exons_ms"), (float(v) for v in ms)))
-        return out
-
-    def free(self):
-        if self.handle:
-            lib().ed_quant_free(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return self._stats("n_probs", "tiles_walked", "tiles_full")
 
 
 def normal_range(chrom_off, start, end, test, ref, phi, expected, rows=None, probs=(0.025, 0.975), layout=0, device=0):

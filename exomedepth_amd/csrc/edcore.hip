@@ -2716,6 +2716,19 @@ static int check_call_rows(const char* entry, const ed_plan* p, const ed_call* r
   return ED_OK;
 }
 
+// rows of (chromosome, first, last) against every sample (the maps of edtotals.inc): a run of exons inside one chromosome of the plan
+static int check_region_rows(const char* entry, const ed_plan* p, const ed_call* rows, int64_t n_rows)
+{
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const int f = edrows::row_fault(rows[r].chrom, rows[r].start_exon, rows[r].end_exon, p->C, p->chrom_off.data());
+    if (f == 1) return ed_fail(ED_ERR_INVALID, "%s: row %lld has first > last", entry, (long long)r);
+    if (f == 2) return ed_fail(ED_ERR_INVALID, "%s: row %lld names a chromosome outside the plan", entry, (long long)r);
+    if (f == 3)
+      return ed_fail(ED_ERR_INVALID, "%s: row %lld does not lie inside its chromosome (it leaves the plan or crosses a boundary)", entry, (long long)r);
+  }
+  return ED_OK;
+}
+
 // The call table is sized by a heuristic when the batch is created; a run that produced more calls than that (up
 // to one per exon is possible) gets a table of the right size and the fill kernel is run again -- the records
 // are a pure function of the packed path.
@@ -3002,8 +3015,9 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edscore.inc"
 #include "edbounds.inc"      // (reads edpost.inc's results) last: a kernel added at the end leaves every other symbol's code where it was (tools/isa_compare.py)
 #include "edmix.inc"         // (edpost.inc's lse3) behind it for the same reason
-#include "edpower.inc"       // (edrefset.inc's wave sum and scan) last again
+#include "edtotals.inc"      // (edrefset.inc's wave sum and scan) the core of the three maps on totals: edpower.inc, edquant.inc, edsim.inc
+#include "edpower.inc"       // last again
 #include "edratio.inc"       // (the call decoration's dd_add) and again
-#include "edquant.inc"       // (edpower.inc's occupancy) and again
+#include "edquant.inc"       // (edtotals.inc's occupancy and CDF walk) and again
 #include "edinflate.inc"     // (nothing of the others) last, for the same reason
-#include "edsim.inc"         // (edpower.inc's occupancy, edannot.inc's scan) and again
+#include "edsim.inc"         // (edtotals.inc's occupancy and CDF walk, edannot.inc's scan) and again

@@ -8,16 +8,14 @@
 // -- `below` and `above` of qbetabinom.ab with R's 1-based indices written out.  No x with C(x) > p (p >= 1, or within rounding of 1):
 // NaN, R's NA, in both.  n = 0: q = p.  Sample s has a = expected (1 - phi) / phi, b = (1 - expected)(1 - phi) / phi in qbetabinom's own
 // operation order (NOT the emissions' shape_params: the same numbers, other roundings), formed on the host.
-// Both depend on the exon through n alone: a sample is walked once per OCCUPIED total.  Occupancy, job list, slots: edpower.inc's, as they are.
+// Both depend on the exon through n alone: a sample is walked once per OCCUPIED total.  Occupancy, job list, slots, the resident map and
+// its look-ups: edtotals.inc's.
 //
-// The walk (bq_walk) is k_pw_walk's for one distribution: L(x) = log pm[x],
-//   L(x + 1) - L(x) = log[(n - x)(a + x) / ((x + 1)(b + n - x - 1))]        L(0) = sum_{k < n} log[(b + k) / (a + b + k)]
-// in tiles of 64 lanes x 4 values; step ratios multiplied four at a time, one logarithm per product, a wave scan of the logarithms on a
-// log-domain carry (P(0) may underflow), exp once per lane, the four masses by products; a second wave scan of the lanes' mass sums on a
-// running carry gives C.  Lane l's C before its first value is carry + scan(l - 1), after its j-th the lane's own partial sum on top of
-// that.  For each probability in turn a ballot finds the first lane whose last C exceeds it; that lane finds the value among its four.  The
-// walk ends with the tile in which the last probability was crossed.  Sums in one fixed order, no atomics on doubles: the bits of a
-// value depend on (n, a, b, p) alone -- not on the other probabilities of the request, which only decide where the walk ends.
+// The walk (bq_walk) takes pm and C from the CDF walk of edtotals.inc (bb_open, bb_step: k_pw_walk's scheme for one distribution), tile
+// by tile: lane l's C before its first value is `excl`, after its j-th the lane's own partial sum part[j] on top of that.  For each
+// probability in turn a ballot finds the first lane whose last C exceeds it; that lane finds the value among its four.  The walk ends
+// with the tile in which the last probability was crossed.  Sums in one fixed order, no atomics on doubles: the bits of a value depend
+// on (n, a, b, p) alone -- not on the other probabilities of the request, which only decide where the walk ends.
 
 namespace {
 
@@ -36,70 +34,31 @@ __device__ __forceinline__ int32_t bq_walk(int64_t n, double a, double b, const 
     }
     return 0;
   }
-  const double size = (double)n, th = a + b;
-  double sl = 0.0;
-  for (int64_t k0 = (int64_t)lane * P; k0 < n; k0 += 64 * P) {
-    double ql = 1.0;
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-      if (k0 + j < n) {
-        const double kd = (double)(k0 + j);
-        ql *= (b + kd) * edfit::frcp(th + kd);
-      }
-    sl += edfit::flog(ql);
-  }
-  double carry_l = pw_wave_sum(sl), carry_c = 0.0;
+  BbWalk w = bb_open(n, a, b, lane);
   int done = 0;
   int32_t tiles = 0;
   const int64_t nt = edpower::n_walk_tiles(n);
   for (int64_t tile = 0; tile < nt && done < K; ++tile) {
     ++tiles;
-    const int64_t xs = tile * edpower::kWalkTile + (int64_t)lane * P;
-    double ql[P + 1];       // products of the step ratios before value j of the lane
-    ql[0] = 1.0;
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      double r = 1.0;
-      if (xs + j < n) {
-        const double xd = (double)(xs + j);
-        const double rest = size - xd - 1.0;
-        r = ((size - xd) * (a + xd)) * edfit::frcp((xd + 1.0) * (b + rest));
-      }
-      ql[j + 1] = ql[j] * r;
-    }
-    const double il = pw_wave_scan(edfit::flog(ql[P]), lane);
-    const double el = __shfl_up(il, 1, 64);                         // the lanes before this one
-    const double pr0 = ed_pexp(lane ? carry_l + el : carry_l);
-    double m[P], part[P];                                           // the lane's masses and their running sums
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      m[j] = xs + j <= n ? pr0 * ql[j] : 0.0;
-      part[j] = j ? part[j - 1] + m[j] : m[j];
-    }
-    const double is = pw_wave_scan(part[P - 1], lane);
-    const double es = __shfl_up(is, 1, 64);
-    const double excl = lane ? carry_c + es : carry_c;              // C before the lane's first value
-    const double incl = excl + part[P - 1];                         // C at its last
+    const BbTile c = bb_step(w, tile, lane);
     while (done < K) {
       const double p = probs[done];
-      const unsigned long long hit = __ballot(p < 1.0 && xs <= n && incl > p);      // (a lane behind n holds no value to cross at)
+      const unsigned long long hit = __ballot(p < 1.0 && c.holds && c.incl > p);
       if (!hit) break;
       if (lane == __ffsll((long long)hit) - 1) {
         // the first of the four whose C exceeds p: the last does
         int j = P - 1;
-        double below = excl + part[P - 2], mass = m[P - 1];
+        double below = c.excl + c.part[P - 2], mass = c.m[P - 1];
 #pragma unroll
         for (int t = P - 2; t >= 0; --t)
-          if (excl + part[t] > p) { j = t; below = t ? excl + part[t - 1] : excl; mass = m[t]; }
+          if (c.excl + c.part[t] > p) { j = t; below = t ? c.excl + c.part[t - 1] : c.excl; mass = c.m[t]; }
         // (a `below` above p, or a mass of 0, can only come from the last bit of the two scans: the value itself then)
         const double frac = mass > 0.0 ? (p - below) * edfit::frcp(mass) : 0.0;
-        q_out[done * stride] = (double)(xs + j) + frac;
+        q_out[done * stride] = (double)(c.xs + j) + frac;
         below_out[done * stride] = below;
       }
       ++done;
     }
-    carry_l += __shfl(il, 63, 64);
-    carry_c += __shfl(is, 63, 64);
   }
   if (lane == 0)
     for (int k = done; k < K; ++k) { q_out[k * stride] = ed_pm_nan(); below_out[k * stride] = ed_pm_nan(); }
@@ -187,20 +146,6 @@ k_bq_obs(const int32_t* __restrict__ test, int layout, int64_t E, int64_t S, int
   }
 }
 
-// the map of s1 - s0 samples, out [2 K][s1 - s0][E]
-__global__ void __launch_bounds__(256)
-k_bq_exons(const int32_t* __restrict__ slot, const int64_t* __restrict__ tab_off, const double* __restrict__ val, int64_t J, int K, int64_t E,
-           int64_t s0, int64_t s1, double* __restrict__ out)
-{
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t ns = s1 - s0;
-  if (i >= ns * E) return;
-  const int64_t s = s0 + i / E;
-  const int32_t sl = slot[s * E + i % E];
-  const int64_t at = tab_off[s] + sl;
-  for (int c = 0; c < 2 * K; ++c) out[c * ns * E + i] = sl < 0 ? ed_pm_nan() : val[c * J + at];
-}
-
 // rows [R] of (chromosome, first, last); a wavefront per (row, sample).  An exon whose total was skipped, or of a sample outside the
 // model, is counted in empty and nowhere else.  The others: bin = the number of k with obs >= cut_of(q_k) (ed_quant_plan.hpp);
 // observed [R][S][K + 1] counts them, expected [R][S][K + 1] adds below_{b+1} - below_b (below_0 = 0, below_{K+1} = 1) in
@@ -267,14 +212,11 @@ k_bq_regions(const ed_call* __restrict__ rows, int64_t R, const int32_t* __restr
 }  // namespace
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-struct ed_quant : PwOccupancy {
-  const ed_plan* plan = nullptr;
+struct ed_quant : TotalsMap {         // d_val [2][K][J]: q, below
   int K = 0;
-  int64_t n_bad = 0, tiles_walked = 0, tiles_full = 0;
-  DevBuf<double> d_val;              // [2][K][J]  q, below
+  int64_t tiles_walked = 0, tiles_full = 0;
   DevBuf<int32_t> d_obs;             // [S][E]  the test counts
   DevBuf<int32_t> d_bad;             // [S]  1: shapes outside the model
-  double ms[4] = {0, 0, 0, 0};       // occupancy, walk, the last regions call's kernels, the last exon map's kernels
 };
 
 // The quantile map of n_samples samples of the plan's exons at probs [n_probs] (HOST; 1 .. 16, finite, inside (0, 1), strictly
@@ -283,38 +225,27 @@ struct ed_quant : PwOccupancy {
 ED_EXPORT int ed_plan_quantile_map(ed_quant** out, const ed_plan* p, const int32_t* test, const int32_t* ref, int counts_on_device, int layout,
                                    const double* phi, const double* expected, const double* probs, int n_probs, int64_t n_samples, void* stream)
 try {
-  if (!out) return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: NULL output");
-  *out = nullptr;
-  if (!p) return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: NULL plan");
-  if (int rc = check_counts_args("ed_plan_quantile_map", layout, n_samples)) return rc;
-  if (!phi || !expected || (p->E > 0 && (!test || !ref))) return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: NULL array");
-  switch (edquant::probs_fault(probs, n_probs)) {
-    case 0: break;
-    case 1: return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: 1 .. %d probabilities are required", edquant::kMaxProbs);
-    case 2: return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: a probability is not finite");
-    case 3: return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: a probability lies outside (0, 1)");
-    default: return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: the probabilities are not strictly ascending");
-  }
-  if (int rc = require_device()) return rc;
-  HIP_TRY(hipSetDevice(p->device));
+  auto own = [&] {
+    switch (edquant::probs_fault(probs, n_probs)) {
+      case 0: return (int)ED_OK;
+      case 1: return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: 1 .. %d probabilities are required", edquant::kMaxProbs);
+      case 2: return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: a probability is not finite");
+      case 3: return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: a probability lies outside (0, 1)");
+      default: return ed_fail(ED_ERR_INVALID, "ed_plan_quantile_map: the probabilities are not strictly ascending");
+    }
+  };
   hipStream_t st = (hipStream_t)stream;
+  DevBuf<int32_t> up_test, up_ref;
+  if (int rc = tm_map_begin("ed_plan_quantile_map", out, p, test, ref, counts_on_device, layout, n_samples, phi, expected, own, up_test, up_ref, st))
+    return rc;
   const int64_t S = n_samples, E = p->E, cells = S * E;
   const int K = n_probs;
   std::unique_ptr<ed_quant> h(new ed_quant);
-  h->plan = p; h->S = S; h->E = E; h->K = K;
+  h->plan = p; h->S = S; h->E = E; h->K = K; h->channels = 2 * K;
   auto nomem = [&](const char* what) { return ed_fail(ED_ERR_NOMEM, "ed_plan_quantile_map: cannot allocate %s", what); };
-
-  DevBuf<int32_t> up_test, up_ref;
-  if (int rc = pw_stage_counts("ed_plan_quantile_map", test, ref, counts_on_device, cells, up_test, up_ref, st)) return rc;
-  // the samples' shapes, qbetabinom's operations in its order (R/tools.R:22-23)
-  std::vector<double> ab((size_t)S * 2);
-  std::vector<int32_t> bad((size_t)S);
-  for (int64_t s = 0; s < S; ++s) {
-    const double a = expected[s] * (1. - phi[s]) / phi[s], b = (1. - expected[s]) * (1. - phi[s]) / phi[s];
-    ab[(size_t)s] = a; ab[(size_t)(S + s)] = b;
-    bad[(size_t)s] = (a > 0.0 && b > 0.0 && a < HUGE_VAL && b < HUGE_VAL) ? 0 : 1;
-    h->n_bad += bad[(size_t)s];
-  }
+  std::vector<double> ab;
+  std::vector<int32_t> bad;
+  h->n_bad = sim_shapes(phi, expected, S, ab, bad);
   DevBuf<double> d_ab, d_probs;
   if (d_ab.alloc((size_t)S * 16) != hipSuccess || d_probs.alloc((size_t)K * 8) != hipSuccess || h->d_bad.alloc((size_t)S * 4) != hipSuccess ||
       h->d_obs.alloc((size_t)std::max<int64_t>(cells, 1) * 4) != hipSuccess)
@@ -370,33 +301,17 @@ ED_EXPORT void ed_quant_free(ed_quant* qm) { delete qm; }
 ED_EXPORT int ed_quant_regions(ed_quant* qm, const ed_call* rows, int64_t n_rows, int32_t* observed, double* expected, int32_t* n_empty,
                                void* stream)
 try {
-  if (!qm) return ed_fail(ED_ERR_INVALID, "ed_quant_regions: NULL map");
-  if (n_rows < 0 || n_rows > (1 << 24)) return ed_fail(ED_ERR_INVALID, "ed_quant_regions: n_rows is outside 0 .. 16777216");
-  if (n_rows > 0 && (!rows || !observed || !expected || !n_empty)) return ed_fail(ED_ERR_INVALID, "ed_quant_regions: NULL array");
-  const ed_plan* p = qm->plan;
-  for (int64_t r = 0; r < n_rows; ++r) {
-    const int f = edrows::row_fault(rows[r].chrom, rows[r].start_exon, rows[r].end_exon, p->C, p->chrom_off.data());
-    if (f == 1) return ed_fail(ED_ERR_INVALID, "ed_quant_regions: row %lld has first > last", (long long)r);
-    if (f == 2) return ed_fail(ED_ERR_INVALID, "ed_quant_regions: row %lld names a chromosome outside the plan", (long long)r);
-    if (f == 3)
-      return ed_fail(ED_ERR_INVALID, "ed_quant_regions: row %lld does not lie inside its chromosome (it leaves the plan or crosses a boundary)",
-                     (long long)r);
-  }
-  if (n_rows == 0) return ED_OK;
-  if (int rc = require_device()) return rc;
-  HIP_TRY(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
+  DevBuf<ed_call> d_rows;
+  if (int rc = tm_regions_begin("ed_quant_regions", qm, rows, n_rows, observed && expected && n_empty, d_rows, st)) return rc;
+  if (n_rows == 0) return ED_OK;
   const int64_t R = n_rows, S = qm->S, KB = qm->K + 1;
   const int64_t sgroups = (S + edpower::kRegionWaves - 1) / edpower::kRegionWaves;
-  if (R * sgroups > 0x7fffffffLL) return ed_fail(ED_ERR_INVALID, "ed_quant_regions: %lld rows x %lld samples are too many for one call", (long long)R, (long long)S);
-  DevBuf<ed_call> d_rows;
   DevBuf<double> d_exp;
   DevBuf<int32_t> d_obs, d_empty;
-  if (d_rows.alloc((size_t)R * sizeof(ed_call)) != hipSuccess || d_exp.alloc((size_t)(R * S * KB) * 8) != hipSuccess ||
-      d_obs.alloc((size_t)(R * S * KB) * 4) != hipSuccess || d_empty.alloc((size_t)R * S * 4) != hipSuccess)
-    return ed_fail(ED_ERR_NOMEM, "ed_quant_regions: cannot allocate %lld rows x %lld samples", (long long)R, (long long)S);
-  HIP_TRY(hipMemcpyAsync(d_rows.get(), rows, (size_t)R * sizeof(ed_call), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (d_exp.alloc((size_t)(R * S * KB) * 8) != hipSuccess || d_obs.alloc((size_t)(R * S * KB) * 4) != hipSuccess ||
+      d_empty.alloc((size_t)R * S * 4) != hipSuccess)
+    return tm_regions_nomem("ed_quant_regions", R, S);
   PwClock clock;
   hipLaunchKernelGGL(k_bq_regions, dim3((unsigned)(R * sgroups)), dim3(edpower::kRegionWaves * 64), 0, st, (const ed_call*)d_rows.get(), R,
                      (const int32_t*)qm->d_slot.get(), (const int32_t*)qm->d_obs.get(), (const int64_t*)qm->d_tab_off.get(),
@@ -414,46 +329,14 @@ ED_CATCH("ed_quant_regions")
 // the model or nothing was crossed.  Made in groups of samples through a bounded device buffer.
 ED_EXPORT int ed_quant_copy_exons(ed_quant* qm, double* out, void* stream)
 try {
-  if (!qm || !out) return ed_fail(ED_ERR_INVALID, "ed_quant_copy_exons: NULL argument");
-  const int64_t S = qm->S, E = qm->E, C2 = 2 * (int64_t)qm->K;
-  if (E == 0) return ED_OK;
-  if (int rc = require_device()) return rc;
-  HIP_TRY(hipSetDevice(qm->plan->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t group = std::max<int64_t>(1, std::min<int64_t>(S, (int64_t)(256 << 20) / (E * C2 * 8)));
-  DevBuf<double> d_out;
-  if (d_out.alloc((size_t)(group * E * C2) * 8) != hipSuccess) return ed_fail(ED_ERR_NOMEM, "ed_quant_copy_exons: cannot allocate %lld samples", (long long)group);
-  double ms = 0;
-  for (int64_t s0 = 0; s0 < S; s0 += group) {
-    const int64_t s1 = std::min(S, s0 + group), ns = s1 - s0;
-    PwClock clock;
-    hipLaunchKernelGGL(k_bq_exons, dim3((unsigned)((ns * E + 255) / 256)), dim3(256), 0, st, (const int32_t*)qm->d_slot.get(),
-                       (const int64_t*)qm->d_tab_off.get(), (const double*)qm->d_val.get(), qm->J, qm->K, E, s0, s1, d_out.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    ms += clock.lap();
-    for (int64_t c = 0; c < C2; ++c)
-      HIP_TRY(hipMemcpyAsync(out + (c * S + s0) * E, d_out.get() + c * ns * E, (size_t)ns * E * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  qm->ms[3] = ms;
-  return ED_OK;
+  return tm_copy_exons("ed_quant_copy_exons", qm, out, stream);
 }
 ED_CATCH("ed_quant_copy_exons")
 
 // One sample's table: *n = its occupied totals; when cap >= *n, totals [*n] (ascending) and values [2][K][cap] (q, then below) to HOST arrays
 ED_EXPORT int ed_quant_copy_table(const ed_quant* qm, int64_t sample, int32_t* totals, double* values, int64_t cap, int64_t* n)
 try {
-  if (!qm || !n || sample < 0 || sample >= qm->S || cap < 0) return ed_fail(ED_ERR_INVALID, "ed_quant_copy_table: bad arguments");
-  const int64_t off = qm->tab_off[(size_t)sample], k = qm->tab_off[(size_t)sample + 1] - off;
-  *n = k;
-  if (cap < k || k == 0) return ED_OK;
-  if (!totals || !values) return ed_fail(ED_ERR_INVALID, "ed_quant_copy_table: NULL array");
-  HIP_TRY(hipSetDevice(qm->plan->device));
-  HIP_TRY(hipMemcpy(totals, qm->d_tab_n.get() + off, (size_t)k * 4, hipMemcpyDeviceToHost));
-  for (int64_t c = 0; c < 2 * (int64_t)qm->K; ++c)
-    HIP_TRY(hipMemcpy(values + c * cap, qm->d_val.get() + c * qm->J + off, (size_t)k * 8, hipMemcpyDeviceToHost));
-  return ED_OK;
+  return tm_copy_table("ed_quant_copy_table", qm, sample, totals, values, cap, n);
 }
 ED_CATCH("ed_quant_copy_table")
 
@@ -462,9 +345,8 @@ ED_CATCH("ed_quant_copy_table")
 ED_EXPORT int ed_quant_stats(const ed_quant* qm, int64_t counts[11], double ms[4])
 try {
   if (!qm || !counts) return ed_fail(ED_ERR_INVALID, "ed_quant_stats: NULL argument");
-  counts[0] = qm->S; counts[1] = qm->E; counts[2] = qm->J; counts[3] = qm->max_jobs; counts[4] = qm->n_skipped; counts[5] = qm->n_bad;
-  counts[6] = qm->largest; counts[7] = qm->words; counts[8] = qm->K; counts[9] = qm->tiles_walked; counts[10] = qm->tiles_full;
-  if (ms) for (int i = 0; i < 4; ++i) ms[i] = qm->ms[i];
+  tm_stats(*qm, counts, ms);
+  counts[8] = qm->K; counts[9] = qm->tiles_walked; counts[10] = qm->tiles_full;
   return ED_OK;
 }
 ED_CATCH("ed_quant_stats")
@@ -474,7 +356,8 @@ ED_CATCH("ed_quant_stats")
 ED_EXPORT int ed_quant_geometry(int32_t out[5])
 try {
   if (!out) return ed_fail(ED_ERR_INVALID, "ed_quant_geometry: NULL output");
-  out[0] = edpower::kWalkTile; out[1] = edpower::kOccCap; out[2] = edpower::kMaxTotal; out[3] = edpower::kRegionTile; out[4] = edquant::kMaxProbs;
+  tm_geometry(out);
+  out[4] = edquant::kMaxProbs;
   return ED_OK;
 }
 ED_CATCH("ed_quant_geometry")

@@ -5,15 +5,17 @@
 //   the draw = the smallest x in 0 .. n with C(x) > u;   n when nothing crosses (u within rounding of 1);   0 for n = 0
 // -- inversion of the distribution function, qbetabinom's `cut` (edquant.inc) at p = u.  The uniform is ed_philox.hpp's: Philox4x32-10 at
 // the counter (exon, global sample, replicate, stream) under the key of a 64-bit seed.  Sample s has a = expected (1 - phi) / phi,
-// b = (1 - expected)(1 - phi) / phi in qbetabinom's own operation order, formed on the host as the quantile map forms them.
+// b = (1 - expected)(1 - phi) / phi in qbetabinom's own operation order, formed on the host by the function the quantile map forms them
+// with (edtotals.inc: sim_shapes).
 //
-// The walk (sim_walk) forms C as bq_walk does, operation for operation: the same step ratios, the same products of four, the same two
-// wave scans and carries, and it locates a uniform with bq_walk's comparisons (incl > u, then excl + part[t] > u).  What differs is how
-// many uniforms one walk serves: the lanes hold up to 64 of them, after each tile every pending uniform the tile can cross is made
-// wave-uniform in turn and located, and the walk ends with the tile in which the last one was crossed.  C does not depend on the uniforms,
-// and a uniform is compared with C alone: the bits of a draw depend on (n, a, b, u) -- not on the other uniforms of the walk, their number
-// or their lanes.  The element-wise kernel is the same function with one uniform in lane 0.
-// The cohort draw walks every sample once per OCCUPIED total (edpower.inc's occupancy, job list and slots, as they are), longest first,
+// The walk (sim_walk) takes C from the CDF walk of edtotals.inc (bb_open, bb_step), the code bq_walk takes it from: C here and C there
+// are the same operations because they are the same source.  It locates a uniform with bq_walk's comparisons (incl > u, then
+// excl + part[t] > u).  What differs is how many uniforms one walk serves: the lanes hold up to 64 of them, after each tile every
+// pending uniform the tile can cross is made wave-uniform in turn and located, and the walk ends with the tile in which the last one
+// was crossed.  C does not depend on the uniforms, and a uniform is compared with C alone: the bits of a draw depend on (n, a, b, u) --
+// not on the other uniforms of the walk, their number or their lanes.  The element-wise kernel is the same function with one uniform in
+// lane 0.
+// The cohort draw walks every sample once per OCCUPIED total (edtotals.inc's occupancy, job list and slots, as they are), longest first,
 // and serves all cells of that (sample, total) from the one walk, 64 at a time.  A job's cells are the inverse of the slot map: count
 // (integer atomics) -> exclusive scan (edannot.inc's) -> fill (an integer cursor per job).  The order in which a job's cells are listed
 // varies from run to run; a cell's draw does not depend on its place in the list.  No atomics on doubles anywhere in this file.
@@ -43,51 +45,13 @@ __device__ __forceinline__ int32_t sim_walk(int64_t n, double a, double b, doubl
   if (n == 0) return 0;
   bool pending = lane < cnt;
   int32_t x = (int32_t)n;                     // nothing crosses: n
-  const double size = (double)n, th = a + b;
-  double sl = 0.0;
-  for (int64_t k0 = (int64_t)lane * P; k0 < n; k0 += 64 * P) {
-    double ql = 1.0;
-#pragma unroll
-    for (int j = 0; j < P; ++j)
-      if (k0 + j < n) {
-        const double kd = (double)(k0 + j);
-        ql *= (b + kd) * edfit::frcp(th + kd);
-      }
-    sl += edfit::flog(ql);
-  }
-  double carry_l = pw_wave_sum(sl), carry_c = 0.0;
+  BbWalk w = bb_open(n, a, b, lane);
   const int64_t nt = edpower::n_walk_tiles(n);
   for (int64_t tile = 0; tile < nt && __ballot(pending); ++tile) {
     ++tiles;
-    const int64_t xs = tile * edpower::kWalkTile + (int64_t)lane * P;
-    double ql[P + 1];       // products of the step ratios before value j of the lane
-    ql[0] = 1.0;
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      double r = 1.0;
-      if (xs + j < n) {
-        const double xd = (double)(xs + j);
-        const double rest = size - xd - 1.0;
-        r = ((size - xd) * (a + xd)) * edfit::frcp((xd + 1.0) * (b + rest));
-      }
-      ql[j + 1] = ql[j] * r;
-    }
-    const double il = pw_wave_scan(edfit::flog(ql[P]), lane);
-    const double el = __shfl_up(il, 1, 64);                         // the lanes before this one
-    const double pr0 = ed_pexp(lane ? carry_l + el : carry_l);
-    double m[P], part[P];                                           // the lane's masses and their running sums
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      m[j] = xs + j <= n ? pr0 * ql[j] : 0.0;
-      part[j] = j ? part[j - 1] + m[j] : m[j];
-    }
-    const double is = pw_wave_scan(part[P - 1], lane);
-    const double es = __shfl_up(is, 1, 64);
-    const double excl = lane ? carry_c + es : carry_c;              // C before the lane's first value
-    const double incl = excl + part[P - 1];                         // C at its last
-    const bool holds = xs <= n;                                     // (a lane behind n holds no value to cross at)
+    const BbTile c = bb_step(w, tile, lane);
     // the largest C any lane of the tile ends on: some lane has incl > u exactly when this has
-    double top = holds ? incl : -1.0;
+    double top = c.holds ? c.incl : -1.0;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) top = __builtin_fmax(top, __shfl_xor(top, d, 64));
     unsigned long long todo = __ballot(pending && top > u);
@@ -95,7 +59,7 @@ __device__ __forceinline__ int32_t sim_walk(int64_t n, double a, double b, doubl
       const int k = __ffsll((long long)todo) - 1;
       todo &= todo - 1;
       const double uk = __shfl(u, k, 64);
-      const unsigned long long hit = __ballot(holds && incl > uk);
+      const unsigned long long hit = __ballot(c.holds && c.incl > uk);
       if (!hit) continue;
       const int first = __ffsll((long long)hit) - 1;
       int32_t xv = 0;
@@ -104,15 +68,13 @@ __device__ __forceinline__ int32_t sim_walk(int64_t n, double a, double b, doubl
         int j = P - 1;
 #pragma unroll
         for (int t = P - 2; t >= 0; --t)
-          if (excl + part[t] > uk) j = t;
-        const int64_t v = xs + j;
+          if (c.excl + c.part[t] > uk) j = t;
+        const int64_t v = c.xs + j;
         xv = (int32_t)(v < n ? v : n);
       }
       const int32_t got = __shfl(xv, first, 64);
       if (lane == k) { x = got; pending = false; }
     }
-    carry_l += __shfl(il, 63, 64);
-    carry_c += __shfl(is, 63, 64);
   }
   return x;
 }
@@ -259,21 +221,6 @@ k_sim_tally(const int32_t* __restrict__ job_s, const int32_t* __restrict__ job_n
 }
 
 thread_local edsim::Stats g_sim_stats;      // of the calling thread's last ed_plan_simulate
-
-// the samples' shapes, qbetabinom's operations in its order (R/tools.R:22-23); returns the samples outside the model
-int64_t sim_shapes(const double* phi, const double* expected, int64_t S, std::vector<double>& ab, std::vector<int32_t>& bad)
-{
-  ab.assign((size_t)S * 2, 0.0);
-  bad.assign((size_t)S, 0);
-  int64_t n_bad = 0;
-  for (int64_t s = 0; s < S; ++s) {
-    const double a = expected[s] * (1. - phi[s]) / phi[s], b = (1. - expected[s]) * (1. - phi[s]) / phi[s];
-    ab[(size_t)s] = a; ab[(size_t)(S + s)] = b;
-    bad[(size_t)s] = (a > 0.0 && b > 0.0 && a < HUGE_VAL && b < HUGE_VAL) ? 0 : 1;
-    n_bad += bad[(size_t)s];
-  }
-  return n_bad;
-}
 
 // what ed_plan_simulate and ed_plan_simulate_cells refuse alike, before anything is enqueued
 int sim_check(const char* entry, const ed_plan* p, const int32_t* test, const int32_t* ref, int64_t n_samples, int64_t sample0, int layout,
@@ -482,7 +429,8 @@ ED_CATCH("ed_sim_stats")
 ED_EXPORT int ed_sim_geometry(int32_t out[5])
 try {
   if (!out) return ed_fail(ED_ERR_INVALID, "ed_sim_geometry: NULL output");
-  out[0] = edpower::kWalkTile; out[1] = edpower::kOccCap; out[2] = edpower::kMaxTotal; out[3] = edpower::kRegionTile; out[4] = edsim::kChunk;
+  tm_geometry(out);
+  out[4] = edsim::kChunk;
   return ED_OK;
 }
 ED_CATCH("ed_sim_geometry")

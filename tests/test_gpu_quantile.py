@@ -548,3 +548,33 @@ def _raw_map(lib, plan, z, layout=0, n_samples=3):
                                        band.ctypes.data, 2, n_samples, None))
     finally:
         assert not h.value
+
+
+# ---- 8. the shared map core -----------------------------------------------------------------------------------------------------
+def test_power_and_quantile_maps_share_their_occupancy(edlib):
+    """A PowerMap and a QuantileMap of the same counts stand on one occupancy (csrc/edtotals.inc: pw_occupy, TotalsMap): every sample's
+    table lists the same totals, and the eight common counters agree but for the samples outside the model, which each map judges by
+    its own shapes -- here both refuse the same one.  Input: tools/dump_total_maps.py's 131 exons x 5 samples, narrow and wide map."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("dump_total_maps", os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools",
+                                                                                  "dump_total_maps.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    g = edlib.quantile_geometry()
+    plan = edlib.Plan(*tool.design())
+    common = ("n_samples", "n_exons", "n_jobs", "max_jobs", "n_skipped", "n_bad_samples", "largest_total", "map_words")
+    for wide in (False, True):
+        test, ref = tool.counts(g, wide)
+        assert test.shape == (131, 5)
+        pm, qm = plan.power_map(test, ref, tool.PHI, tool.EXPECTED), plan.quantile_map(test, ref, tool.PHI, tool.EXPECTED)
+        ps, qs = pm.stats(), qm.stats()
+        assert [ps[k] for k in common] == [qs[k] for k in common], (ps, qs)
+        assert ps["n_skipped"] == 1 and ps["n_bad_samples"] == 1 and ps["largest_total"] == (g["max_total"] if wide else g["occupancy_cap"] - 1)
+        for s in range(5):
+            tp, tq = pm.table(s)["totals"], qm.table(s)["totals"]
+            assert tp.dtype == tq.dtype == np.int32 and np.array_equal(tp, tq), s
+            assert set(tool.edge_totals(g, wide)) <= set(tp.tolist())
+        pm.free()
+        qm.free()
+    plan.close()

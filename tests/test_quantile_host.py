@@ -175,10 +175,21 @@ def test_interface_declares_the_quantile_entries():
     assert "ed_quant_free" in names and re.search(r"\bvoid ed_quant_free\(", header) and "ED_EXPORT void ed_quant_free(" in source
     core = open(os.path.join(ROOT, "exomedepth_amd", "csrc", "edcore.hip")).read()
     assert '#include "edquant.inc"' in core and '#include "ed_quant_plan.hpp"' in core
-    for k in ("k_bq_walk", "k_bq_points", "k_bq_exons", "k_bq_regions"):
+    for k in ("k_bq_walk", "k_bq_points", "k_bq_regions"):
         assert k in source, k
-    for k in ("k_pw_scan", "k_pw_mark", "k_pw_rank", "k_pw_jobs", "k_pw_slots"):      # the occupancy passes are the power map's, not copies
-        assert not re.search(r"^%s\(" % k, source, flags=re.M), k
+    csrc = os.path.join(ROOT, "exomedepth_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".inc", ".hpp", ".h"))}
+    totals = texts["edtotals.inc"]
+    assert core.index('#include "edtotals.inc"') < core.index('#include "edpower.inc"') < core.index('#include "edquant.inc"')
+    # the occupancy passes, the exon kernel and the CDF walk are the shared core's (edtotals.inc): defined there once, used here, not copied
+    for k in ("k_pw_scan", "k_pw_mark", "k_pw_rank", "k_pw_jobs", "k_pw_slots", "k_tm_exons", "bb_open", "bb_step"):
+        assert len(re.findall(r"^(?:__device__ __forceinline__ \w+ )?%s\(" % k, totals, flags=re.M)) == 1, k
+        assert not re.search(r"^(?:__device__ __forceinline__ \w+ )?%s\(" % k, source, flags=re.M), k
+    assert "pw_occupy(" in source and "tm_copy_exons(" in source and "bb_open(" in source and "bb_step(" in source
+    assert "k_bq_exons" not in "".join(texts.values()) and "k_pw_exons" not in "".join(texts.values())
+    # one step ratio under csrc/: the quantile map and the draws form C from the same source
+    ratio = "frcp((xd + 1.0) * (b + rest))"
+    assert {f: t.count(ratio) for f, t in texts.items() if ratio in t} == {"edtotals.inc": 1}
     plan = open(os.path.join(ROOT, "exomedepth_amd", "csrc", "ed_quant_plan.hpp")).read()
     assert "hip" not in plan.lower().replace("no hip", "") and "kMaxProbs = 16" in plan
     import exomedepth_amd

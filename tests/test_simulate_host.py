@@ -170,6 +170,13 @@ def test_interface_declares_the_simulate_entries():
     for k in ("k_pw_scan", "k_pw_mark", "k_pw_rank", "k_pw_jobs", "k_pw_slots", "k_annot_scan_block"):      # used, not copied
         assert not re.search(r"^%s\(" % k, source, flags=re.M), k
     assert "pw_occupy(" in source and "k_annot_scan_block" in source
+    # the CDF walk and the samples' shapes are the shared core's (edtotals.inc, in front of the three maps): used here, not restated
+    totals = open(os.path.join(ROOT, "exomedepth_amd", "csrc", "edtotals.inc")).read()
+    assert core.index('#include "edtotals.inc"') < core.index('#include "edsim.inc"')
+    for k, ret in (("bb_open", "BbWalk"), ("bb_step", "BbTile"), ("sim_shapes", "int64_t")):
+        assert len(re.findall(r"^(?:__device__ __forceinline__ )?%s %s\(" % (ret, k), totals, flags=re.M)) == 1, k
+        assert not re.search(r"^(?:__device__ __forceinline__ )?%s %s\(" % (ret, k), source, flags=re.M) and k + "(" in source, k
+    assert "frcp((xd + 1.0) * (b + rest))" not in source and totals.count("frcp((xd + 1.0) * (b + rest))") == 1
     hdr = open(os.path.join(ROOT, "exomedepth_amd", "csrc", "ed_philox.hpp")).read()
     assert "#include <hip" not in hdr and "0xD2511F53" in hdr and "0xCD9E8D57" in hdr and "0x9E3779B9" in hdr and "0xBB67AE85" in hdr
     import exomedepth_amd
