@@ -9,6 +9,7 @@ from .api import (Batch, Cohort, MultiDevice, DeviceArray, device_count, PinnedA
                   correct_counts_using_PCA, pca_gram, pca_last_info,
                   Annotation, annotate_calls, cohort_call_recurrence, annot_geometry,
                   ReadCounter, getBamCounts, count_everted_reads, bed_targets, readcount_geometry,
+                  GcCounter, gc_content, gc_geometry,
                   CALL_BOUNDS_DTYPE,
                   PowerMap, detection_power, region_runs, power_geometry, power_from_moments, POWER_DTYPE,
                   QuantileMap, normal_range, qbetabinom, qbetabinom_ab, quantile_geometry,
@@ -21,6 +22,7 @@ __all__ = ["Batch", "Cohort", "MultiDevice", "DeviceArray", "device_count", "Pin
            "correct_counts_using_PCA", "pca_gram", "pca_last_info",
            "Annotation", "annotate_calls", "cohort_call_recurrence", "annot_geometry",
            "ReadCounter", "getBamCounts", "count_everted_reads", "bed_targets", "readcount_geometry",
+           "GcCounter", "gc_content", "gc_geometry",
            "CALL_BOUNDS_DTYPE",
            "PowerMap", "detection_power", "region_runs", "power_geometry", "power_from_moments", "POWER_DTYPE",
            "QuantileMap", "normal_range", "qbetabinom", "qbetabinom_ab", "quantile_geometry",

@@ -238,6 +238,12 @@ SYMBOLS = [
     ("ed_plan_simulate_cells", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, C.c_uint64, _i64, C.c_uint32, _vp, _vp, _vp]),
     ("ed_sim_stats", C.c_int, [_vp, _vp]),
     ("ed_sim_geometry", C.c_int, [C.POINTER(_i32)]),
+    ("ed_gc_create", C.c_int, [C.POINTER(_vp), C.c_int, _i64]),
+    ("ed_gc_destroy", None, [_vp]),
+    ("ed_gc_add", C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    ("ed_gc_copy", C.c_int, [_vp, _vp, _vp]),
+    ("ed_gc_kernel_ms", C.c_int, [_vp, C.POINTER(_dbl)]),
+    ("ed_gc_geometry", C.c_int, [C.POINTER(_i32)]),
 ]
 
 

@@ -3460,6 +3460,129 @@ def bed_targets(bed_frame=None, bed_file=None, include_chr=False, reorder=True):
     return out
 
 
+def gc_geometry():
+    """{block, segment_bytes, step_bytes, lane_bytes} of the letter counter (ed_gc_geometry): for tests placing shapes on the edges"""
+    out = (C.c_int32 * 4)()
+    check(lib().ed_gc_geometry(out))
+    return dict(zip(("block", "segment_bytes", "step_bytes", "lane_bytes"), (int(v) for v in out)))
+
+
+class GcCounter:
+    """Letters of byte ranges of a file, summed per target on the device (ed_gc): add() takes one piece of the file and the ranges that touch
+    it, counts() gives int32 (gc, atgc) per target -- #{C, G} and #{A, C, G, T}, either case; every other byte counts in neither."""
+
+    def __init__(self, n_targets, device=0):
+        self.n = int(n_targets)
+        self.handle = C.c_void_p()
+        check(lib().ed_gc_create(C.byref(self.handle), int(device), self.n))
+
+    def close(self):
+        if self.handle:
+            lib().ed_gc_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _open(self):
+        if not self.handle:
+            raise EdError("GcCounter is closed")
+
+    def add(self, data, file_offset, first, last_excl, target):
+        """data: the file's bytes [file_offset, file_offset + len(data)) (bytes, or a uint8 array); first, last_excl: file byte addresses of the
+        ranges, which may reach beyond the piece on either side (they are clipped to it); target: the index each range adds to"""
+        self._open()
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        first, last_excl, target = (np.ascontiguousarray(a, dtype=np.int64).ravel() for a in (first, last_excl, target))
+        if not (first.size == last_excl.size == target.size):
+            raise ValueError("first, last_excl and target must have the same length")
+        check(lib().ed_gc_add(self.handle, _ptr(buf) if buf.size else None, int(buf.size), int(file_offset), int(first.size),
+                              _ptr(first) if first.size else None, _ptr(last_excl) if first.size else None, _ptr(target) if first.size else None))
+
+    def counts(self):
+        self._open()
+        gc, atgc = np.empty(self.n, np.int32), np.empty(self.n, np.int32)
+        check(lib().ed_gc_copy(self.handle, _ptr(gc) if self.n else None, _ptr(atgc) if self.n else None))
+        return gc, atgc
+
+    def kernel_ms(self):
+        """k_gc_count device milliseconds of this counter so far"""
+        self._open()
+        ms = C.c_double(0)
+        check(lib().ed_gc_kernel_ms(self.handle, C.byref(ms)))
+        return ms.value
+
+
+def gc_content(fasta, chromosome, start, end, *, flank=0, counts=False, batch_bytes=64 << 20, device=0, stats=None):
+    """GC content of every target [start, end] (1-based, both included: the count frame's own columns) of the uncompressed FASTA file `fasta` (a
+    path or a fasta.FastaIndex), counted on the device: float64 gc / atgc, where gc counts the letters G and C and atgc the letters A, T, G and C,
+    in either case -- letterFrequency(x, "GC") / letterFrequency(x, "ATGC") of the reference's referenceFasta block (R/countBamInGranges.R:333-344).
+    N, the IUPAC codes and everything else count in neither; a target without any of the four letters gives NaN (NA in R), which the caller drops
+    or imputes before using the column as a covariate.  counts=True: the int32 arrays (gc, atgc) instead.
+    flank widens every target by that many bases on both sides, clipped to its sequence.  The file is read in pieces of batch_bytes, two in flight
+    (the next is read while the one before is uploaded and counted); a piece goes to the device with the ranges that touch it, and a target cut by
+    a piece's border is the sum of its parts, so no result depends on batch_bytes.  Sequences without a target are not read.
+    stats: a dict that receives pieces, bytes_read and kernel_ms (k_gc_count's device time), for tools/bench_gc.py.
+    ValueError: a sequence the file does not have, a target beyond its sequence's end, start < 1, end < start."""
+    from . import fasta as _fasta
+    idx = fasta if isinstance(fasta, _fasta.FastaIndex) else _fasta.FastaIndex(fasta)
+    flank, batch_bytes = int(flank), int(batch_bytes)
+    if flank < 0 or batch_bytes < 1:
+        raise ValueError("flank >= 0 and batch_bytes >= 1 wanted")
+    chrom = [str(c) for c in chromosome]
+    start = np.asarray(start).astype(np.int64).ravel()
+    end = np.asarray(end).astype(np.int64).ravel()
+    if not (len(chrom) == start.size == end.size):
+        raise ValueError("chromosome, start and end must have the same length")
+    n = start.size
+    if n:
+        first, last = idx.byte_range(chrom, start, end)                # the targets as given: refusals name the caller's rows
+        if flank:
+            length = idx.length[idx.rows(chrom)]
+            first, last = idx.byte_range(chrom, np.maximum(start - flank, 1), np.minimum(end + flank, length))
+    else:
+        first = last = np.zeros(0, np.int64)
+    counter = GcCounter(n, device=device)
+    pieces = bytes_read = 0
+    try:
+        if n:
+            order = np.argsort(first, kind="stable")
+            sf, sl = first[order], last[order]
+            reach = np.maximum.accumulate(sl)                          # ascending, like sf: what searchsorted needs
+            # a sequence's bytes lie together in the file, so the sorted ranges are grouped by sequence: one stretch of the file -- from its
+            # first target's first byte to its targets' last -- per sequence that holds a target
+            seq = idx.rows(chrom)[order]
+            cut = np.flatnonzero(seq[1:] != seq[:-1]) + 1
+            lo_of, hi_of = sf[np.r_[0, cut]], reach[np.r_[cut - 1, n - 1]]
+            with open(idx.path, "rb") as f:
+                for a, b in zip(lo_of.tolist(), hi_of.tolist()):
+                    for p in range(a, b, batch_bytes):
+                        q = min(p + batch_bytes, b)
+                        i0 = int(np.searchsorted(reach, p, side="right"))      # the ranges before end at or before p
+                        i1 = int(np.searchsorted(sf, q, side="left"))          # the ranges from here on begin at or after q
+                        if i0 >= i1:
+                            continue                                           # a piece between targets
+                        f.seek(p)
+                        data = f.read(q - p)
+                        if len(data) != q - p:
+                            raise ValueError("%s ends before byte %d: the file does not fit its index" % (idx.path, q))
+                        counter.add(data, p, sf[i0:i1], sl[i0:i1], order[i0:i1])
+                        pieces, bytes_read = pieces + 1, bytes_read + len(data)
+        gc, atgc = counter.counts()
+        if stats is not None:
+            stats.update(pieces=pieces, bytes_read=bytes_read, kernel_ms=counter.kernel_ms())
+    finally:
+        counter.close()
+    if counts:
+        return gc, atgc
+    out = np.full(n, np.nan)
+    np.divide(gc, atgc, out=out, where=atgc > 0)
+    return out
+
+
 def _count_bams(frame, bam_files, mode, min_mapq, read_width, device, inflate="host"):
     from . import bam as _bam
     if inflate not in ("host", "device"):
@@ -3505,15 +3628,21 @@ def _count_bams(frame, bam_files, mode, min_mapq, read_width, device, inflate="h
 
 
 def getBamCounts(bed_frame=None, bed_file=None, bam_files=(), index_files=None, min_mapq=20, read_width=300, include_chr=False, device=0,
-                 inflate="host"):
+                 inflate="host", reference_fasta=None):
     """reference R/countBamInGranges.R:298-370: the exon x sample count frame from BAM files and a BED frame, counted on the device.
     Returns a dict of columns in the reference's order -- chromosome, start (BED start + 1), end, exon when the frame has a fourth text column,
-    then one int32 array per basename(bam) -- with rows in the reference's order (bed_targets).  A fragment per record as include/exomedepth_amd.h
-    states it ("Reads per exon", mode 0); every target chromosome must be named in each BAM header (ValueError).  index_files is accepted and
-    ignored: the whole file is scanned, which gives the same counts.  GC content (referenceFasta) is not computed.
+    GC when reference_fasta is given, then one int32 array per basename(bam) -- with rows in the reference's order (bed_targets).  A fragment per
+    record as include/exomedepth_amd.h states it ("Reads per exon", mode 0); every target chromosome must be named in each BAM header
+    (ValueError).  index_files is accepted and ignored: the whole file is scanned, which gives the same counts.
+    reference_fasta (the reference's referenceFasta): an uncompressed FASTA file, or a fasta.FastaIndex; the frame gains the float64 column GC,
+    the fraction of G and C among the A, T, G and C of every re-ordered target, counted on the device (gc_content) before any BAM file is opened.
+    A target without any of the four letters has NaN (NA in R): drop or impute it before the column serves as a covariate
+    (ExomeDepth(..., data={"GC": ...}, formula="cbind(test, reference) ~ GC")).  Without the argument the frame has no such column.
     inflate: "host" (the default) inflates the files' BGZF blocks on the host's thread pool; "device" sends them to the device compressed and
     inflates, scans and gathers them there (bam.DeviceBamFile, ReadCounter.add_device) -- the same frame and the same errors for the same files; the headers are checked on the host first."""
     frame = bed_targets(bed_frame, bed_file, include_chr=include_chr, reorder=True)
+    if reference_fasta is not None:
+        frame["GC"] = gc_content(reference_fasta, frame["chromosome"], frame["start"], frame["end"], device=device)
     return _count_bams(frame, bam_files, 0, min_mapq, read_width, device, inflate)
 
 

@@ -3021,3 +3021,4 @@ ED_CATCH("ed_batch_stage_ms")
 #include "edquant.inc"       // (edtotals.inc's occupancy and CDF walk) and again
 #include "edinflate.inc"     // (nothing of the others) last, for the same reason
 #include "edsim.inc"         // (edtotals.inc's occupancy and CDF walk, edannot.inc's scan) and again
+#include "edgc.inc"          // (nothing of the others) and again

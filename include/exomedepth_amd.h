@@ -1180,6 +1180,39 @@ int ed_readcount_add_device(ed_readcount* rc, int32_t column, int mode, int64_t 
                             const int32_t* d_tlen, const uint32_t* d_flag_mapq, int32_t n_ref, const int32_t* ref_to_chrom, int32_t min_mapq,
                             int32_t read_width, void* ready_stream);
 
+/* =====================================================================================
+ * GC content of every target: getBamCounts' referenceFasta (reference R/countBamInGranges.R:333-344) -- csrc/edgc.inc
+ * ===================================================================================== */
+
+/* Two sums per target over a range [first, last_excl) of FILE byte addresses, the byte folded to lower case (| 0x20):
+ *   gc    the bytes 'c' and 'g';    atgc    the bytes 'a', 'c', 'g' and 't'
+ * -- exactly the eight letters AaCcGgTt.  N, the IUPAC codes, line ends and every other byte count in neither, which is letterFrequency(x, "GC") and
+ * letterFrequency(x, "ATGC") on the reference's DNAString; the GC column is gc / atgc, NA where atgc == 0.  Nothing here knows about FASTA: which
+ * bytes belong to a target (a record's offset and line geometry; the line ends inside a target are part of its range and are not letters) is the
+ * caller's business (exomedepth_amd/fasta.py).
+ *
+ * ed_gc_create: n_targets >= 0; both sums start at zero.
+ * ed_gc_add: one chunk of the file -- bytes[0, n_bytes) (HOST) are the file's bytes [file_offset, file_offset + n_bytes) -- and n_ranges ranges,
+ * which may reach beyond the chunk on either side or miss it: the kernel clips each to the chunk and ADDS what it finds to gc[target] and
+ * atgc[target].  A target cut by chunk borders is the sum of its pieces, a target given twice in one chunk is counted twice, and a range of
+ * megabases is shared among many wavefronts (a segment each).  Integer adds only: the sums are the same bits whatever the cuts, the order of the
+ * ranges or the launch geometry.  The chunk is staged through two pinned sets, at most 64 MiB a part, so the upload of one part
+ * runs under the kernel of the part before; only the bytes the ranges span are uploaded; the call returns when the last part has been queued.
+ * ED_ERR_INVALID before any device work: a target outside [0, n_targets), first > last_excl, a negative size or offset.  n_ranges == 0 and
+ * n_bytes == 0 are valid.  A sum is int32: a target has fewer than 2^31 letters.
+ * ed_gc_copy: the two sums to the host, [n_targets] each, everything queued complete.  ed_gc_kernel_ms: device time of the object's k_gc_count
+ * launches so far (waits for them).  An object is not for two threads at a time; it sets its device on every call. */
+typedef struct ed_gc ed_gc;
+int ed_gc_create(ed_gc** gc, int device, int64_t n_targets);
+void ed_gc_destroy(ed_gc* gc);
+int ed_gc_add(ed_gc* gc, const uint8_t* bytes, int64_t n_bytes, int64_t file_offset, int64_t n_ranges, const int64_t* first,
+              const int64_t* last_excl, const int64_t* target);
+int ed_gc_copy(ed_gc* gc, int32_t* gc_out, int32_t* atgc_out);
+int ed_gc_kernel_ms(ed_gc* gc, double* ms);
+/* Launch geometry, for tests that place their shapes on its edges: out = {B, S, W, L}.  k_gc_count has B threads a workgroup, a wavefront of which
+ * takes one segment of S bytes of one range, W bytes a step, a lane L bytes at an L-byte aligned address.  No result depends on them. */
+int ed_gc_geometry(int32_t out[4]);
+
 /* ---- utilities ---- */
 /* device memory through the library, for callers without a HIP binding (tests, R shim) */
 int ed_malloc(void** dptr, size_t bytes);
